@@ -16,11 +16,16 @@ parameters.
 
 ``--model lenet`` benchmarks the reference LeNet at the reference batch (32/rank).
 
-At world size > 1 (or with ``--force-comm``) the JSON line also proves the run was what it
-claims: ``distinct_gpus`` (device UUIDs gathered from every rank), ``rccl_world`` (the
-RCCL communicator's size), ``replicas_in_sync`` (MIN == MAX over ranks of two checksums of
-the flat parameters after the timed steps) and ``phases_ms`` (forward / backward compute /
-communication left exposed after backward / optimizer, HIP events over a few extra steps).
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON line.
+``--dump-outputs DIR`` also writes what the last timed step produced (``loss.npy``,
+``params.npy``); the inputs are seeded, so two builds can be compared output for output.
+
+``--full`` adds what takes work of its own: ``param_checksum``, ``phases_ms`` (forward /
+backward compute / communication left exposed after backward / optimizer, HIP events over a
+few extra steps) and, at world size > 1 (or with ``--force-comm``), the proof that the run
+was what it claims: ``distinct_gpus`` (device UUIDs gathered from every rank),
+``rccl_world`` (the RCCL communicator's size), ``replicas_in_sync`` (MIN == MAX over ranks
+of two checksums of the flat parameters after the timed steps).
 """
 from __future__ import annotations
 
@@ -72,10 +77,21 @@ def parse():
                     help="activation dtype; default bf16 for resnet18 (always), fp32 for "
                          "lenet (the reference dtype; bf16 = BASELINE config 3)")
     ap.add_argument("--bucket-mb", type=float, default=25.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-phase "
+                         "breakdown (--phases), the checksum of the parameters after the timed "
+                         "steps ('param_checksum') and, with communication, the replica check "
+                         "('distinct_gpus', 'rccl_world', 'replicas_in_sync').  Off by default: a "
+                         "plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step produced to "
+                         "DIR/<name>.npy (float32): 'loss' (the value the step returns) and "
+                         "'params' (the flat parameters the step updated in place; a fixed "
+                         "seeded sample of them above 64 MB).  Rank 0 writes")
     ap.add_argument("--phases", type=int, default=-1,
-                    help="after the timed run, N extra eager steps timed per phase with HIP "
-                         "events (fwd, bwd compute, exposed comm, optimizer) -> 'phases_ms'; "
-                         "-1 = auto (5 on the native backend)")
+                    help="with --full: after the timed run, N extra eager steps timed per phase "
+                         "with HIP events (fwd, bwd compute, exposed comm, optimizer) -> "
+                         "'phases_ms'; -1 = auto (5 on the native backend)")
     ap.add_argument("--small-allreduce", default="auto", choices=["auto", "rccl", "xgmi"],
                     help="buckets <= 4 MB via the one-shot xGMI peer-memory kernel.  auto: "
                          "LeNet (207 KB of gradients, SURVEY 2.4's design point) uses it when "
@@ -398,17 +414,19 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     final_loss = float(loss)
-    # checksum of the flat fp32 parameters after the timed steps (float64 sums): equal bits
-    # give equal values, so two runs of the same step sequence can be compared exactly
-    pflat = model.flat.data if getattr(model, "flat", None) is not None else torch.cat(
-        [p.detach().reshape(-1) for p in model.parameters()])
-    pw = (torch.arange(pflat.numel(), device=pflat.device, dtype=torch.float64) % 251) + 1.0
-    param_checksum = [float(pflat.double().sum()), float((pflat.double() * pw).sum())]
-    verify = verify_replicas(model, dev) if comm else None
-    if a.phases < 0:
-        a.phases = 5 if a.backend == "native" else 0
-    phases = None
-    if a.phases > 0 and a.backend == "native":
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, model)
+    param_checksum = verify = phases = None
+    if a.full:
+        # checksum of the flat fp32 parameters after the timed steps (float64 sums): equal bits
+        # give equal values, so two runs of the same step sequence can be compared exactly
+        pflat = flat_params(model)
+        pw = (torch.arange(pflat.numel(), device=pflat.device, dtype=torch.float64) % 251) + 1.0
+        param_checksum = [float(pflat.double().sum()), float((pflat.double() * pw).sum())]
+        verify = verify_replicas(model, dev) if comm else None
+        if a.phases < 0:
+            a.phases = 5 if a.backend == "native" else 0
+    if a.full and a.phases > 0 and a.backend == "native":
         if loader is not None:
             src = [next_batch() for _ in range(2)]
         else:
@@ -463,13 +481,14 @@ def main():
                 "sampler": ("MySampler(partition)" if loader is not None else None),
             },
             "final_loss": round(final_loss, 4),
-            "param_checksum": param_checksum,
             "peak_mem_gb": round(torch.cuda.max_memory_reserved() / 2**30, 1),
             "peak_alloc_gb": round(torch.cuda.max_memory_allocated() / 2**30, 1),
             # allocator retries (a failed hipMalloc frees the cache and synchronises): >0
             # means the step ran short of device memory
             "alloc_retries": int(torch.cuda.memory_stats().get("num_alloc_retries", 0)),
         }
+        if param_checksum is not None:
+            res["param_checksum"] = param_checksum
         if verify is not None:
             res.update(verify)
         res.update(checks)
@@ -479,6 +498,33 @@ def main():
             res["phases_ms"] = phases
         print(json.dumps(res), flush=True)
     env.destroy()
+
+
+def flat_params(model):
+    if getattr(model, "flat", None) is not None:
+        return model.flat.data
+    return torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+
+
+DUMP_BUDGET = 64 * 10**6 - 4096  # array bytes over all dumped files (room for the headers)
+
+
+def dump_outputs(path, loss, model):
+    """What the last timed step handed back, as float32 ``.npy`` files: ``loss`` (the step's
+    return value) and ``params`` (the flat parameters it updated in place).  Parameters beyond
+    the byte budget are reduced to a fixed seeded sample of their elements, in index order."""
+    import numpy as np
+
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    lo = loss.detach().float().reshape(-1).cpu().numpy()
+    p = flat_params(model).detach().float().reshape(-1).cpu().numpy()
+    room = (DUMP_BUDGET - lo.nbytes) // 4
+    if p.size > room:
+        idx = np.sort(np.random.default_rng(0).choice(p.size, size=room, replace=False))
+        p = p[idx]
+    np.save(out / "loss.npy", lo)
+    np.save(out / "params.npy", p)
 
 
 def verify_replicas(model, dev):

@@ -102,7 +102,7 @@ class Reducer {
     // them: one cross-queue wait instead of one per bucket (each ~5-10 us of barrier-packet
     // latency on the step's critical tail).  Sync-launched buckets are already on this stream.
     for (size_t b = 0; b < buckets_.size(); ++b) {
-      if (works_[b] && (!single_wait_ || (int64_t)b == last_async_)) works_[b]->wait();
+      if (works_[b] && (!single_wait_ || (int64_t)b == last_async_)) wait_nogil(works_[b]);
       at::Tensor view = buf_.slice(0, buckets_[b].lo, buckets_[b].hi);
       if (comm_[b].defined()) {
         view.copy_(comm_[b]);
@@ -148,6 +148,13 @@ class Reducer {
     int64_t lo, hi, nparams, pending;
   };
 
+  // A blocking wait (gloo) must not hold the GIL: the backend's worker thread can need it to
+  // complete the very operation waited for (torch's own Work.wait binding releases it too).
+  static void wait_nogil(const c10::intrusive_ptr<c10d::Work>& w) {
+    py::gil_scoped_release nogil;
+    w->wait();
+  }
+
   void launch(int64_t b) {
     if (launched_[b]) return;
     launched_[b] = true;
@@ -184,7 +191,7 @@ class Reducer {
     // them): the current stream first waits for the last asynchronous one still in flight on
     // the communication stream (every earlier one precedes it there).
     opts.asyncOp = !sync_launch_;
-    if (sync_launch_ && last_async_ >= 0 && works_[last_async_]) works_[last_async_]->wait();
+    if (sync_launch_ && last_async_ >= 0 && works_[last_async_]) wait_nogil(works_[last_async_]);
     if (use_avg_ && avg_scale_ != 1.0) {
       opts.reduceOp = c10d::ReduceOp(c10d::ReduceOp::AVG);
       scaled_[b] = true;

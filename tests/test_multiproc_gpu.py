@@ -349,7 +349,8 @@ def test_bench_two_ranks(tmp_path):
                    OMP_NUM_THREADS="2")
         procs.append(subprocess.Popen(
             [sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-             "--res", "64", "--batch", "8"], cwd=tmp_path, env=env, stdout=subprocess.PIPE,
+             "--res", "64", "--batch", "8", "--full"], cwd=tmp_path, env=env,
+            stdout=subprocess.PIPE,
             stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=300) for p in procs]
     for p, (o, e) in zip(procs, outs):
@@ -419,7 +420,7 @@ def test_bench_lenet_two_ranks_graph(tmp_path, corrupt):
             env["DMLAB_SELFCHECK_CORRUPT"] = corrupt
         procs.append(subprocess.Popen(
             [sys.executable, str(root / "bench.py"), "--gpus", "2", "--model", "lenet", "--steps",
-             "20", "--warmup", "5", "--fused", "1"], cwd=tmp_path,
+             "20", "--warmup", "5", "--fused", "1", "--full"], cwd=tmp_path,
             env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=300) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-2000:] for o in outs]

@@ -245,7 +245,7 @@ def test_bench_lenet_graph_steps_bit_equal(tmp_path):
     out = []
     for k in (25, 1):
         r = subprocess.run([sys.executable, str(root / "bench.py"), "--model", "lenet",
-                            "--warmup", "25", "--steps", "1900", "--phases", "0",
+                            "--warmup", "25", "--steps", "1900", "--full", "--phases", "0",
                             "--graph-steps", str(k)], cwd=tmp_path, capture_output=True,
                            text=True, timeout=300, env=dict(os.environ))
         assert r.returncode == 0, r.stderr[-2000:]

@@ -64,7 +64,7 @@ def _bench(args, timeout=400):
     env = dict(os.environ, PYTHONPATH=str(ROOT))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), str(ROOT / "bench.py"),
-           "--gpus", "1", "--force-comm", "1"] + args
+           "--gpus", "1", "--force-comm", "1", "--full"] + args
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
