@@ -85,12 +85,6 @@ void rows_mean(at::Tensor x, at::Tensor out, double scale) {
                 (float)scale, cur_stream());
 }
 
-void scale_inplace(at::Tensor x, double s) {
-  CHECK_CUDA(x); CHECK_F32(x); CHECK_CONTIG(x);
-  const DeviceGuard guard(x.device());
-  dm::scale_inplace(x.data_ptr<float>(), x.numel(), (float)s, cur_stream());
-}
-
 // ------------------------------------------------------------------ small conv (LeNet)
 inline bool is_bf16(const at::Tensor& t) { return t.scalar_type() == at::kBFloat16; }
 inline void check_act(const at::Tensor& t, const char* n) {
@@ -216,10 +210,6 @@ std::vector<int64_t> cu_mask_of(int64_t stream, int64_t words) {
               hipSuccess, "hipExtStreamGetCUMask failed");
   return std::vector<int64_t>(m.begin(), m.end());
 }
-void stream_destroy(int64_t stream) {
-  TORCH_CHECK(hipStreamDestroy((hipStream_t)(uintptr_t)stream) == hipSuccess);
-}
-
 // ------------------------------------------------------------ xGMI one-/two-shot all-reduce
 int64_t xgmi_alloc(int64_t bytes) { return (int64_t)(uintptr_t)dm::xgmi_alloc((size_t)bytes); }
 void xgmi_free(int64_t ptr) { dm::xgmi_free((void*)(uintptr_t)ptr); }
@@ -418,12 +408,6 @@ void lenet_fused_step(at::Tensor x, at::Tensor labels, std::vector<at::Tensor> w
                        cur_stream(), pr);
 }
 
-int num_cus(int device) {
-  int n = 0;
-  TORCH_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess);
-  return n;
-}
-
 }  // namespace
 
 void register_resnet(pybind11::module_& m);
@@ -439,12 +423,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_resnet(m);
   register_reducer(m);
   m.doc() = "dmlab native HIP kernels for MI355X (gfx950)";
-  m.def("num_cus", &num_cus);
   m.def("sgd_step", &sgd_step, "fused flat SGD/GD step");
   m.def("adam_step", &adam_step, "fused flat Adam step");
   m.def("cast_f32_bf16", &cast_f32_bf16, "fp32 -> bf16 cast");
   m.def("rows_mean", &rows_mean, "[rows,N] -> [N] scaled row sum");
-  m.def("scale_inplace", &scale_inplace, "x *= s");
   m.def("conv_small_fwd", &conv_small_fwd);
   m.def("conv_small_bwd", &conv_small_bwd);
   m.def("conv_small_workspace", &conv_small_workspace);
@@ -456,7 +438,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bias_act", &bias_act, py::arg("y"), py::arg("bias"), py::arg("out"), py::arg("relu"));
   m.def("cu_mask_stream", &cu_mask_stream);
   m.def("cu_mask_of", &cu_mask_of);
-  m.def("stream_destroy", &stream_destroy);
   m.def("xgmi_alloc", &xgmi_alloc);
   m.def("xgmi_free", &xgmi_free);
   m.def("xgmi_get_handle", &xgmi_get_handle);

@@ -56,6 +56,15 @@ dm::ConvGeom fwd_geom(const at::Tensor& x, int Cout, int KH, int KW, int stride,
 
 int64_t conv_stats_rows(int64_t M, int64_t cfg, int64_t ncols);
 
+// A 1-bit mask over the elements of `of` (bit j of byte i = element 8i + j), or null
+const unsigned char* bit_mask(const c10::optional<at::Tensor>& m, const at::Tensor& of,
+                              const char* n) {
+  if (!m.has_value()) return nullptr;
+  TORCH_CHECK(m->is_cuda() && m->scalar_type() == at::kByte && m->is_contiguous() &&
+                  m->numel() * 8 >= of.numel(), n, ": uint8 [numel/8] on the device");
+  return m->data_ptr<uint8_t>();
+}
+
 // The folded BatchNorm-backward operand (kernels.h BnBwdIn) of a data / weight gradient whose
 // dY argument is that BN's OUTPUT gradient dz: y (its input, dz's shape), coef [3][C] (bn_backward
 // with dy None), scale/shift (ReLU mask from y) or the 1-bit mask, neither: no ReLU
@@ -193,9 +202,11 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
   // dy2 / wd2 (optional, stride 2): a 1x1/s2/p0 projection's output gradient and packed data-
   // gradient weights [Cin][1][1][C2]; its data gradient is merged into this launch (parity
   // class (0,0) gets a second K segment), so dx is written once, complete
-  // red_* (optional, cfg 80 only): the backward reduction of the BatchNorm + ReLU whose
-  // output gradient dx is (its input red_y, forward scale/shift, mean/invstd) runs in this
-  // dgrad's epilogue -> red_part [res64_grid(M)][2][Cin] (bn_backward's pre_slab)
+  // red_* (optional; stride 1: cfg 80, 90-93 or 42; stride 2: a complete data gradient on cfg
+  // 11-17 or 90-93): the backward reduction of the BatchNorm + ReLU whose output gradient dx is
+  // (its input red_y, forward scale/shift, mean/invstd, optionally the 1-bit red_mask instead
+  // of the mask from red_y) runs in this dgrad's epilogue -> red_part [rows][2][Cin]
+  // (bn_backward's pre_slab; rows = conv_stats_rows, stride 2: dgrad_s2_red_rows)
   // add_mask (optional, stride 1): 1-bit mask of `add` (bit j of byte i = element 8i + j), so
   // the identity-skip gradient dres = add * mask is added without being materialised
   need_bf16_nhwc(dy, "dy");
@@ -219,15 +230,24 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
   base.N = N; base.H = OH; base.W = OW; base.C = Cout; base.lgC8 = ilog2(Cout / 8);
   base.OH = H; base.OW = W; base.OC = Cin;
   base.KW = KW; base.Ncols = Cin; base.wK = KH * KW * Cout;
-  const unsigned char* addm = nullptr;
-  if (add_mask.has_value()) {
+  if (add_mask.has_value())
     TORCH_CHECK(addp && stride == 1 && addp != bp(dx),
                 "add_mask needs a separate add tensor and a stride-1 data gradient");
-    TORCH_CHECK(add_mask->is_cuda() && add_mask->scalar_type() == at::kByte &&
-                    add_mask->is_contiguous() && add_mask->numel() * 8 >= dx.numel(),
-                "add_mask: uint8 [numel/8] on the device");
-    addm = add_mask->data_ptr<uint8_t>();
-  }
+  const unsigned char* addm = bit_mask(add_mask, dx, "add_mask");
+  // the red_* operands, checked against dx and the launch's part rows
+  auto red_in = [&](int64_t rows) {
+    need_bf16_nhwc(*red_y, "red_y");
+    TORCH_CHECK(red_y->sizes() == dx.sizes(), "red_y: dx's shape");
+    TORCH_CHECK(red_scale && red_shift && red_mean && red_invstd && red_part,
+                "red_*: scale, shift, mean, invstd and part are all required");
+    need_f32(*red_scale, "red_scale", Cin);
+    need_f32(*red_shift, "red_shift", Cin);
+    need_f32(*red_mean, "red_mean", Cin);
+    need_f32(*red_invstd, "red_invstd", Cin);
+    need_f32(*red_part, "red_part", rows * 2 * Cin);
+    return dm::BnBwdRed{bp(*red_y), bit_mask(red_mask, dx, "red_mask"), fp(*red_scale),
+                        fp(*red_shift), fp(*red_mean), fp(*red_invstd), fp(*red_part)};
+  };
   dm::BnBwdIn bwd{};
   const bool has_bwd = bwd_y.has_value();
   if (has_bwd) {
@@ -254,24 +274,7 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
       const bool halo = cfg == 42 && dm::halo_cfg((int)cfg, hbn, hwv) && dm::conv_halo_supported(g);
       TORCH_CHECK(cfg == 80 || pipe || halo,
                   "red_*: a cfg 80, pipelined (90-93) or cfg 42 data gradient");
-      need_bf16_nhwc(*red_y, "red_y");
-      TORCH_CHECK(red_y->sizes() == dx.sizes(), "red_y: dx's shape");
-      TORCH_CHECK(red_scale && red_shift && red_mean && red_invstd && red_part,
-                  "red_*: scale, shift, mean, invstd and part are all required");
-      need_f32(*red_scale, "red_scale", Cin);
-      need_f32(*red_shift, "red_shift", Cin);
-      need_f32(*red_mean, "red_mean", Cin);
-      need_f32(*red_invstd, "red_invstd", Cin);
-      need_f32(*red_part, "red_part", conv_stats_rows(g.M, cfg, Cin) * 2 * Cin);
-      const unsigned char* rmask = nullptr;
-      if (red_mask.has_value()) {
-        TORCH_CHECK(red_mask->is_cuda() && red_mask->scalar_type() == at::kByte &&
-                        red_mask->is_contiguous() && red_mask->numel() * 8 >= dx.numel(),
-                    "red_mask: uint8 [numel/8] on the device");
-        rmask = red_mask->data_ptr<uint8_t>();
-      }
-      const dm::BnBwdRed red{bp(*red_y), rmask, fp(*red_scale), fp(*red_shift), fp(*red_mean),
-                             fp(*red_invstd), fp(*red_part)};
+      const dm::BnBwdRed red = red_in(conv_stats_rows(g.M, cfg, Cin));
       if (pipe)
         dm::conv_pipe(bp(dy), bp(wd), bp(dx), addp, nullptr, g, (int)cfg, st, &red);
       else if (halo)
@@ -337,6 +340,9 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
     TORCH_CHECK(wd2.has_value() && wd2->scalar_type() == at::kBFloat16 && wd2->is_contiguous() &&
                     wd2->numel() == (int64_t)Cin * dy2->size(3),
                 "wd2 must be bf16 [Cin][1][1][C2]");
+    // the kernels address both through 32-bit buffer ranges (x2bytes / w2bytes below)
+    TORCH_CHECK(dy2->numel() * 2 < (1LL << 31) && wd2->numel() * 2 < (1LL << 31),
+                "dy2 / wd2: each must be below 2 GiB");
     // class (a, b) = (0, 0) is geometry 0 (the a-major loop above): rows (y, x) are the output
     // pixels (2y, 2x), read dY at (y, x) through the centre tap -- the 1x1/s2/p0 map
     TORCH_CHECK(set.g[0].oy0 == 0 && set.g[0].ox0 == 0 && set.g[0].Hg == OH && set.g[0].Wg == OW,
@@ -352,26 +358,8 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
     TORCH_CHECK((multi_igemm || multi_pipe) && !accumulate && !any_empty && ng == 4,
                 "red_* with stride 2: a complete data gradient (all 4 parity classes, no add) on "
                 "an igemm (cfg 11-17) or pipelined (cfg 90-93) tile");
-    need_bf16_nhwc(*red_y, "red_y");
-    TORCH_CHECK(red_y->sizes() == dx.sizes(), "red_y: dx's shape");
-    TORCH_CHECK(red_scale && red_shift && red_mean && red_invstd && red_part,
-                "red_*: scale, shift, mean, invstd and part are all required");
-    need_f32(*red_scale, "red_scale", Cin);
-    need_f32(*red_shift, "red_shift", Cin);
-    need_f32(*red_mean, "red_mean", Cin);
-    need_f32(*red_invstd, "red_invstd", Cin);
-    need_f32(*red_part, "red_part",
-             (multi_pipe ? dm::pipe_multi_rows(set, ng) : dm::igemm_multi_rows(set, ng, (int)cfg)) *
-                 2 * Cin);
-    const unsigned char* rmask = nullptr;
-    if (red_mask.has_value()) {
-      TORCH_CHECK(red_mask->is_cuda() && red_mask->scalar_type() == at::kByte &&
-                      red_mask->is_contiguous() && red_mask->numel() * 8 >= dx.numel(),
-                  "red_mask: uint8 [numel/8] on the device");
-      rmask = red_mask->data_ptr<uint8_t>();
-    }
-    const dm::BnBwdRed red{bp(*red_y), rmask, fp(*red_scale), fp(*red_shift), fp(*red_mean),
-                           fp(*red_invstd), fp(*red_part)};
+    const dm::BnBwdRed red = red_in(multi_pipe ? dm::pipe_multi_rows(set, ng)
+                                               : dm::igemm_multi_rows(set, ng, (int)cfg));
     const bool ok = multi_pipe
         ? dm::conv_pipe_multi(bp(dy), bp(wd), bp(dx), nullptr, set, ng, (int)cfg, st,
                               merged ? &seg2 : nullptr, &red)
@@ -506,17 +494,6 @@ void pack_weights(at::Tensor w, at::Tensor wf, c10::optional<at::Tensor> wd, int
 }
 
 // ------------------------------------------------------------------ BN
-// every conv layer's weight packing in one launch (see pack_weights_multi_kernel)
-void pack_weights_multi(at::Tensor desc, at::Tensor prefix, int64_t total) {
-  TORCH_CHECK(desc.is_cuda() && prefix.is_cuda() && desc.scalar_type() == at::kLong &&
-              prefix.scalar_type() == at::kLong, "desc/prefix: int64 device tensors");
-  const int nl = prefix.numel() - 1;
-  TORCH_CHECK(nl >= 1 && nl <= 32 && desc.numel() == 8 * nl, "pack_weights_multi: 1..32 layers");
-  const DeviceGuard guard(desc.device());
-  dm::pack_weights_multi((const long long*)desc.data_ptr(), (const long long*)prefix.data_ptr(), nl,
-                         total, cur_stream());
-}
-
 // LDS-tiled variant: tprefix[l] = first 32x32 (co, ci) tile of layer l
 void pack_weights_tiled(at::Tensor desc, at::Tensor tprefix, int64_t ntiles) {
   TORCH_CHECK(desc.is_cuda() && tprefix.is_cuda() && desc.scalar_type() == at::kLong &&
@@ -632,15 +609,6 @@ void stem_bwd_fused(at::Tensor y, at::Tensor mean, at::Tensor invstd, at::Tensor
   dm::wgrad_reduce_s2d(fp(slab), S, C, (int)Cin, xs.size(3), fp(dw), (float)wbeta, st);
 }
 
-
-void wgrad_reduce_s2d(at::Tensor slab, int64_t S, int64_t Cout, int64_t Cin, int64_t Cp,
-                      at::Tensor dw, double beta) {
-  need_f32(slab, "slab", S * Cout * 16 * Cp);
-  need_f32(dw, "dw", Cout * Cin * 49);
-  const DeviceGuard guard(slab.device());
-  dm::wgrad_reduce_s2d(fp(slab), (int)S, (int)Cout, (int)Cin, (int)Cp, fp(dw), (float)beta,
-                       cur_stream());
-}
 
 void bn_backward(c10::optional<at::Tensor> dout, c10::optional<at::Tensor> out, at::Tensor y,
                  at::Tensor mean, at::Tensor invstd, at::Tensor gamma, at::Tensor dgamma,
@@ -843,7 +811,6 @@ ImgView img_view(const at::Tensor& img) {
 
 bool stem_fused_supported(int64_t Hin, int64_t Win) { return dm::stem_fused_supported(Hin, Win); }
 int64_t stem_fused_grid(int64_t N) { return dm::stem_fused_grid((int)N); }
-int64_t stem_slab_cols() { return dm::stem_slab_cols(); }
 // floats of the backward's slab workspace for `grid` workgroups: D and G partials + their sums
 int64_t stem_bwd_slab_len(int64_t grid) {
   const int64_t gk = dm::stem_gram_cols();
@@ -982,7 +949,6 @@ void register_resnet(pybind11::module_& m) {
         py::arg("bwd_scale") = py::none(), py::arg("bwd_shift") = py::none(),
         py::arg("bwd_mask") = py::none());
   m.def("pack_weights", &pack_weights);
-  m.def("pack_weights_multi", &pack_weights_multi);
   m.def("pack_weights_tiled", &pack_weights_tiled);
   m.def("bn_stats_finalize", &bn_stats_finalize, py::arg("stats"), py::arg("T"), py::arg("count"),
         py::arg("gamma"), py::arg("beta"), py::arg("rmean"), py::arg("rvar"), py::arg("momentum"),
@@ -999,7 +965,6 @@ void register_resnet(pybind11::module_& m) {
         py::arg("shift"), py::arg("pdy"), py::arg("pidx"), py::arg("pre_slab"), py::arg("pre_rows"),
         py::arg("xs"), py::arg("Cin"), py::arg("dw"), py::arg("wbeta"), py::arg("work"),
         py::arg("slab"));
-  m.def("wgrad_reduce_s2d", &wgrad_reduce_s2d);
   m.def("bn_backward", &bn_backward, py::arg("dout"), py::arg("out"), py::arg("y"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"), py::arg("dgamma"), py::arg("dbeta"), py::arg("gbeta"), py::arg("mode"), py::arg("scale"), py::arg("shift"), py::arg("pdy"), py::arg("pidx"), py::arg("K"), py::arg("S"), py::arg("P"), py::arg("dy"), py::arg("dres"), py::arg("work"),
         py::arg("pre_slab") = py::none(), py::arg("pre_rows") = 0, py::arg("mask") = py::none());
   m.def("bn_relu_maxpool", &bn_relu_maxpool, py::arg("y"), py::arg("scale"), py::arg("shift"),
@@ -1018,7 +983,6 @@ void register_resnet(pybind11::module_& m) {
   m.def("pack_weights_s2d", &pack_weights_s2d);
   m.def("stem_fused_supported", &stem_fused_supported);
   m.def("stem_fused_grid", &stem_fused_grid);
-  m.def("stem_slab_cols", &stem_slab_cols);
   m.def("stem_bwd_slab_len", &stem_bwd_slab_len);
   m.def("stem_fwd_fused", &stem_fwd_fused, py::arg("img"), py::arg("idx"), py::arg("nsc"),
         py::arg("nbi"), py::arg("wk"), py::arg("gamma"), py::arg("pext"), py::arg("code"),

@@ -10,8 +10,6 @@
 // branch gradient dz when the block has a skip connection.
 #include "common.h"
 
-#include <cstdlib>
-
 namespace dm {
 
 __device__ __forceinline__ void unpack8(const uint4& v, float f[8]) {
@@ -64,7 +62,7 @@ __global__ void __launch_bounds__(256) slab_colsum_kernel(const float* __restric
 // Σ over the G rows of part[G][2C] for channels c (Σ) and C+c (second moment): NT/CH row
 // lanes x CH channels per block, 8 loads in flight per lane, lanes combined in a fixed order
 // (groups of RLN/16 lanes, then the 16 groups); the result is valid in threads 0..CH-1
-// (channel blockIdx.x*CH + threadIdx.x).  CH = 4 (64 row lanes) sums up to fin_direct_rows()
+// (channel blockIdx.x*CH + threadIdx.x).  CH = 4 (64 row lanes) sums up to FIN_DIRECT_ROWS
 // rows without the slab_colsum pre-pass: one dependent launch fewer per finalize, in 4-wave
 // blocks (a 1024-thread block waited for a whole free CU next to the side stream: 23 us)
 constexpr int FIN_CH = 16;
@@ -105,19 +103,13 @@ __device__ __forceinline__ void block_sum2(const float* __restrict__ part, int G
     }
 }
 
-// rows a 4-channel finalize block sums directly (DMLAB_FIN_DIRECT, default 2048; 256 = the
-// round-4 path: slab_colsum pre-pass above 256 rows)
-static int fin_direct_rows() {
-  static const int v = [] {
-    const char* e = getenv("DMLAB_FIN_DIRECT");
-    return e ? atoi(e) : 2048;
-  }();
-  return v;
-}
+// rows a 4-channel finalize block sums directly; larger slabs take the slab_colsum pre-pass
+// (the round-4 threshold was 256 rows; the A/B switch was removed after the measurement)
+constexpr int FIN_DIRECT_ROWS = 2048;
 
 // level-1 groups for a [T][2C] slab: none when the finalize block can sum it directly
 static inline int colsum_groups(int T) {
-  return (T <= 256 || T <= fin_direct_rows()) ? 0 : min(256, (T + 31) / 32);
+  return T <= FIN_DIRECT_ROWS ? 0 : min(256, (T + 31) / 32);
 }
 
 // Per-channel finalize math of the forward / backward finalize kernels (the one-launch

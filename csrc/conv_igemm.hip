@@ -527,38 +527,6 @@ __global__ void __launch_bounds__(256) pack_weights_any_kernel(const float* __re
   }
 }
 
-// All conv layers of a model in one launch: desc[l] = {w, wf, wd, Cout, Cin, Cpad, KH, KW}
-// (pointers as int64), prefix[l] = first packed element of layer l (prefix[nl] = total).
-__global__ void __launch_bounds__(256) pack_weights_multi_kernel(const long long* __restrict__ desc,
-                                                                 const long long* __restrict__ prefix,
-                                                                 int nl) {
-  __shared__ long long pre[33];
-  for (int i = threadIdx.x; i <= nl; i += blockDim.x) pre[i] = prefix[i];
-  __syncthreads();
-  const long long total = pre[nl];
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += stride) {
-    int l = 0;
-    while (l + 1 < nl && o >= pre[l + 1]) ++l;
-    const long long* d = desc + 8 * l;
-    const float* w = (const float*)d[0];
-    bf16_t* wf = (bf16_t*)d[1];
-    bf16_t* wd = (bf16_t*)d[2];
-    const int Cout = (int)d[3], Cin = (int)d[4], Cpad = (int)d[5], KH = (int)d[6], KW = (int)d[7];
-    const unsigned e = (unsigned)(o - pre[l]);
-    const int ci = (int)(e % (unsigned)Cpad);
-    unsigned t = e / (unsigned)Cpad;
-    const int kw = (int)(t % (unsigned)KW);
-    t /= (unsigned)KW;
-    const int kh = (int)(t % (unsigned)KH);
-    const int co = (int)(t / (unsigned)KH);
-    const float v = ci < Cin ? w[(((long long)co * Cin + ci) * KH + kh) * KW + kw] : 0.f;
-    const bf16_t b = f2bf(v);
-    wf[e] = b;
-    if (wd && ci < Cin) wd[(((long long)ci * KH + kh) * KW + kw) * Cout + co] = b;
-  }
-}
-
 // All conv layers in one launch, LDS-tiled: block = (layer, 32 co, 32 ci) over all taps
 // (tap chunks of <= 9).  Reads are contiguous OIHW runs of 32*T floats, both packed
 // layouts are written as contiguous 64-B rows (2 bf16 per lane), so neither the strided
@@ -642,11 +610,6 @@ __global__ void __launch_bounds__(256) pack_weights_tiled_kernel(const long long
       }
     }
   }
-}
-
-void pack_weights_multi(const long long* desc, const long long* prefix, int nl, long long total,
-                        hipStream_t st) {
-  pack_weights_multi_kernel<<<grid_for(total, 256, 8192), 256, 0, st>>>(desc, prefix, nl);
 }
 
 void pack_weights_tiled(const long long* desc, const int* tprefix, int nl, int ntiles,

@@ -17,7 +17,6 @@ void adam_step(float* p, const float* g, float* m, float* v, bf16_t* pbf, long l
 void cast_f32_bf16(const float* x, bf16_t* y, long long n, hipStream_t st);
 void rows_mean(const float* x, float* out, int rows, long long n, float scale,
                hipStream_t st);
-void scale_inplace(float* x, long long n, float s, hipStream_t st);
 
 }  // namespace dm
 
@@ -183,8 +182,6 @@ void wgrad_res64(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom&
 void wgrad_halo(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
                 long long mchunk, int nty, hipStream_t st, const float* pre_sc = nullptr,
                 const float* pre_sh = nullptr, const BnBwdIn* bwd = nullptr);
-void pack_weights_multi(const long long* desc, const long long* prefix, int nl, long long total,
-                        hipStream_t st);
 void pack_weights_tiled(const long long* desc, const int* tprefix, int nl, int ntiles,
                         hipStream_t st);
 int igemm_fwd_rowtile(int cfg);

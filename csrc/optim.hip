@@ -132,13 +132,6 @@ __global__ void __launch_bounds__(256) rows_mean_kernel(const float* __restrict_
   }
 }
 
-__global__ void __launch_bounds__(256) scale_kernel(float* __restrict__ x, long long n,
-                                                    float s) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    x[i] *= s;
-}
-
 // ---------------------------------------------------------------- launchers
 void sgd_step(float* p, const float* g, float* mom, bf16_t* pbf, long long n, float lr,
               float momentum, float dampening, float wd, float gscale, bool nesterov,
@@ -185,11 +178,6 @@ void rows_mean(const float* x, float* out, int rows, long long n, float scale,
                hipStream_t st) {
   if (n <= 0) return;
   rows_mean_kernel<<<grid_for(n, 256), 256, 0, st>>>(x, out, rows, n, scale);
-}
-
-void scale_inplace(float* x, long long n, float s, hipStream_t st) {
-  if (n <= 0) return;
-  scale_kernel<<<grid_for(n, 256), 256, 0, st>>>(x, n, s);
 }
 
 }  // namespace dm

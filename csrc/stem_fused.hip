@@ -39,10 +39,7 @@
 // and recomputing y for an in-place dy tile (slower: a conflicted read-modify-write epilogue).
 // stem_slab_reduce_kernel + stem_wcombine_kernel sum the per-workgroup slabs in fixed order
 // and form the OIHW gradient.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+#include <type_traits>
 
 #include "common.h"
 #include "igemm_common.h"
@@ -77,15 +74,6 @@ struct RawUnit {
 // Workgroup barrier for LDS hand-offs only: waits for this wave's LDS operations, not its
 // global loads (__syncthreads' fence drains vmcnt too, which would expose the raw-row and
 // pooled-row prefetches -- issued a step ahead -- at every step boundary).
-// s_memtime stamp (timing experiments: DMLAB_STEM_TRACE); one asm statement with its wait
-__device__ __forceinline__ unsigned long long stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-
 __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
@@ -348,7 +336,6 @@ struct StemFwdArgs {
   uint8_t* code;         // [N][PH][PW][32]: window codes, 4 bits per channel (see wcode)
   float* stats;          // [grid][2][64] or nullptr
   int N, nimg;           // batch rows, image rows (idx values are clamped to it)
-  int ablate;            // timing experiments only (DMLAB_STEM_ABLATE): skip parts of the work
   StemGeo G;
 };
 
@@ -422,7 +409,7 @@ __global__ void __launch_bounds__(FNT, 1) stem_fwd_kernel(StemFwdArgs a) {
       ring_rows(ro, 4 * i - 3 + 2 * slot, G.ROWB);  // conv row 2i + slot: input rows 2oy-3 ..
 #pragma unroll
       for (int mb = 0; mb < 4; ++mb) {
-        if (32 * mb >= G.Wout || (a.ablate & 1)) break;
+        if (32 * mb >= G.Wout) break;
         const int px = 32 * mb + (lane & 31);
         const int pxb = min(px, G.Wout - 1);
         f32x16 acc = conv_tile<4>(wa, E, ro, pxb * 48, hh);
@@ -531,7 +518,7 @@ __global__ void __launch_bounds__(FNT, 1) stem_fwd_kernel(StemFwdArgs a) {
     // (a) pooling of the pair the MFMA waves computed in the previous step
     if (st >= 1) {
       const int ps = st - 1, pq = ps / SPI, pk = ps - pq * SPI;
-      if (pk >= 2 && pact && !(a.ablate & 4)) {
+      if (pk >= 2 && pact) {
         const int i = pk - 2;
         const unsigned char* Yt = Y + (ps & 1) * YB;
         if (i == 0) {
@@ -578,7 +565,7 @@ __global__ void __launch_bounds__(FNT, 1) stem_fwd_kernel(StemFwdArgs a) {
       }
     }
     // (b) E rows for the next step's MFMA, from the raw rows staged in the previous step
-    if (st < nsteps && !(a.ablate & 8)) {
+    if (st < nsteps) {
       const bf16_t* Sp = S + ((st - 1) & 1) * SB;
       if (kk == 0) em.build(E, Sp, G, -3, 7, -3);
       else if (kk == 1) em.build(E, Sp, G, 4, 2, 0);
@@ -753,9 +740,7 @@ struct StemBwdArgs2 {
   float* dslab;          // [grid][64][SKH]: D = dz^T X partials
   float* gslab;          // [grid][GK][GK]: G = X^T X partials (upper-triangle tiles)
   int N, nimg;
-  int ablate;            // timing experiments only (DMLAB_STEM_ABLATE)
   int split;             // m-steps of a pair's MFMA work before the mid-step barrier
-  unsigned long long* trace;  // timing experiments: [step][8] stamps of workgroup 0
   StemGeo G;
 };
 
@@ -804,14 +789,11 @@ __global__ void __launch_bounds__(BNT, 1) stem_bwd_kernel(StemBwdArgs2 a) {
     em.init(tid, G.Wout);  // busier side): rows of pair kk-2 from the S rows stored this step
     auto run = [&](auto wtag) {
       constexpr int W = decltype(wtag)::value;
-      const bool tr = a.trace && blockIdx.x == 0 && W == 0;
       for (int st = 0; st <= nsteps; ++st) {
-        if (tr) a.trace[st * 8 + 4] = stamp();
         lds_barrier();  // step start: T[(st-1) & 1] (dz of the pair) and its E rows are ready
-        if (tr) a.trace[st * 8 + 5] = stamp();
         const int ps = st - 1;
         const int pk = ps >= 0 ? ps % SPI : -1;
-        const bool work = ps >= 0 && pk >= 2 && !(a.ablate & 1);
+        const bool work = ps >= 0 && pk >= 2;
         const unsigned char* Tt = T + (ps & 1) * TB;
         // the VALU waves' gather runs before the mid-step barrier, their staging after it:
         // m-steps [0, split) of the 2 * Wout / 16 before, the rest after
@@ -820,16 +802,14 @@ __global__ void __launch_bounds__(BNT, 1) stem_bwd_kernel(StemBwdArgs2 a) {
           gram_slot<W>(acc, Tt, E, G, pk - 2, 0, 0, min(split, nt), lane);
           if (split > nt) gram_slot<W>(acc, Tt, E, G, pk - 2, 1, 0, split - nt, lane);
         }
-        if (tr) a.trace[st * 8 + 6] = stamp();
         lds_barrier();  // mid-step
-        if (tr) a.trace[st * 8 + 7] = stamp();
         if (work) {
           if (split < nt) gram_slot<W>(acc, Tt, E, G, pk - 2, 0, split, nt, lane);
           gram_slot<W>(acc, Tt, E, G, pk - 2, 1, max(split - nt, 0), nt, lane);
         }
         // E rows: kk = 1 -> rows -3..1 (S rows 0..1), kk = i + 2 -> rows 4i+2..4i+5 (pair i's
         // new rows; pair i-1's 4i-7..4i+1 are being read: 13 live rows, the ring)
-        if (st < nsteps && !(a.ablate & 8)) {
+        if (st < nsteps) {
           const int kk = st % SPI;
           if (kk == 1) em.build(E, S, G, -3, 5, -3);
           else if (kk >= 2) em.build(E, S, G, 4 * (kk - 2) + 2, 4, 0);
@@ -938,14 +918,11 @@ __global__ void __launch_bounds__(BNT, 1) stem_bwd_kernel(StemBwdArgs2 a) {
     }
     return bcur;
   };
-  const bool trv = a.trace && blockIdx.x == 0 && vt < 64;
   // raw rows: stored into S before the mid-step barrier of step kk (the MFMA waves expand them
   // after it), loaded during step kk - 1: kk = 1 rows 0..1, kk = i + 2 rows 4i+2..4i+5
   for (int st = 0; st <= nsteps; ++st) {
     const int q = st / SPI, kk = st - q * SPI;
-    if (trv) a.trace[st * 8 + 0] = stamp();
     lds_barrier();  // (MFMA waves: step start)
-    if (trv) a.trace[st * 8 + 1] = stamp();
     // ---- phase 1 (MFMA waves: the first m-steps of the previous step's pair)
     if (st < nsteps) {
       if (kk == 0) {
@@ -965,12 +942,10 @@ __global__ void __launch_bounds__(BNT, 1) stem_bwd_kernel(StemBwdArgs2 a) {
         rm.store<DT>(ru, S, G.SP, 4);  // rows 4i+2..4i+5
         // the quad's 4 windows: pooled rows i (+1), columns qb (+1); channels 0..3 of the
         // chunk now, 4..7 after the mid-step barrier (each half reloads its windows)
-        if (pl && !(a.ablate & 4)) gquad(gres, i, 0);
+        if (pl) gquad(gres, i, 0);
       }
     }
-    if (trv) a.trace[st * 8 + 2] = stamp();
     lds_barrier();  // (MFMA waves: mid-step) this step's S and pooled-ring reads are done
-    if (trv) a.trace[st * 8 + 3] = stamp();
     // ---- phase 2 (MFMA waves: the rest of the pair, then the E expansion)
     if (st < nsteps) {
       if (kk == 0) {
@@ -979,7 +954,7 @@ __global__ void __launch_bounds__(BNT, 1) stem_bwd_kernel(StemBwdArgs2 a) {
         rm.load<DT>(ru, a.img, base(q), G.Hin, G.Win, 2, 4);
       } else {
         const int i = kk - 2;
-        if (pl && !(a.ablate & 4)) {
+        if (pl) {
           uint2 r1[4];
           gquad(r1, i, 1);
           // whole 16-byte chunks: 8-lane groups of ds_write_b128 fill a pixel row, conflict-free
@@ -989,9 +964,6 @@ __global__ void __launch_bounds__(BNT, 1) stem_bwd_kernel(StemBwdArgs2 a) {
           for (int pp = 0; pp < 4; ++pp)
             *reinterpret_cast<uint4*>(Tt + toff[pp]) = make_uint4(gres[pp].x, gres[pp].y, r1[pp].x, r1[pp].y);
         }
-        if (trv) a.trace[16384 + st * 4 + 0] = stamp();
-        if (trv) a.trace[16384 + st * 4 + 1] = stamp();
-        if (trv) a.trace[16384 + st * 4 + 2] = stamp();
         if (i + 1 < G.PH) rm.load<DT>(ru, a.img, base(q), G.Hin, G.Win, 4 * i + 6, 4);
       }
     }
@@ -1088,25 +1060,12 @@ static size_t bwd_smem(const StemGeo& G) {
          (size_t)PRING * G.PW * SCO * 2 + (size_t)PRING * G.PW * SCO / 2;
 }
 
-// DMLAB_STEM_ABLATE=<bits>: timing experiments (wrong results): 1 conv MFMAs, 2 wgrad MFMAs,
-// 4 pooling / gather, 8 E expansion
-static int stem_ablate() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DMLAB_STEM_ABLATE");
-    v = e ? atoi(e) : 0;
-  }
-  return v;
-}
-
 int stem_fused_grid(int N) {
   static int cus = 0;
   if (!cus) {
     int dev = 0;
     DM_CHECK(hipGetDevice(&dev));
     DM_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const char* e = getenv("DMLAB_STEM_GRID");  // tuning: workgroups (default one per CU)
-    if (e && atoi(e) > 0 && atoi(e) < cus) cus = atoi(e);
   }
   return N < cus ? N : cus;
 }
@@ -1130,7 +1089,6 @@ void stem_fwd_fused(const void* img, int dtype, const long long* idx, const floa
   a.N = N;
   a.nimg = nimg;
   a.G = stem_geo(Hin, Win);
-  a.ablate = stem_ablate();
   const size_t sm = fwd_smem(a.G);
 #define DM_SF(DT)                                              \
   do {                                                         \
@@ -1172,24 +1130,8 @@ void stem_bwd_fused2(const void* img, int dtype, const long long* idx, const flo
   a.N = N;
   a.nimg = nimg;
   a.G = stem_geo(Hin, Win);
-  a.ablate = stem_ablate();
-  {
-    static int sp = -1;
-    if (sp < 0) {
-      const char* e = getenv("DMLAB_STEM_SPLIT");  // tuning: default 10 of 14 at W 224
-      sp = e ? atoi(e) : 0;
-    }
-    a.split = sp > 0 ? sp : (2 * (a.G.Wout >> 4) * 5 + 6) / 7;
-  }
-  static unsigned long long* trace_buf = nullptr;
-  const bool trace = getenv("DMLAB_STEM_TRACE") != nullptr;
-  const int nst = ((N + grid - 1) / grid) * (a.G.PH + 2) + 1;
-  if (trace && !trace_buf) {
-    DM_CHECK(hipMalloc(&trace_buf, 8 * 8 * 4096));
-    DM_CHECK(hipMemset(trace_buf, 0, 8 * 8 * 4096));
-  }
-  // [0, nst*8) per-step stamps, [16384, 16384 + nst*4) the second region: disjoint for nst <= 2048
-  a.trace = trace && nst <= 2048 ? trace_buf : nullptr;
+  // the mid-step barrier after 5/7 of a pair's m-steps (10 of 14 at W 224)
+  a.split = (2 * (a.G.Wout >> 4) * 5 + 6) / 7;
   const size_t sm = bwd_smem(a.G);
 #define DM_SB(DT)                                              \
   do {                                                         \
@@ -1201,45 +1143,6 @@ void stem_bwd_fused2(const void* img, int dtype, const long long* idx, const flo
   else DM_SB(2);
 #undef DM_SB
   DM_CHECK(hipGetLastError());
-  if (a.trace) {  // per-step medians of workgroup 0's phases (s_memtime units)
-    std::vector<unsigned long long> h((size_t)nst * 8), h2((size_t)nst * 4);
-    DM_CHECK(hipStreamSynchronize(st));
-    DM_CHECK(hipMemcpy(h.data(), a.trace, h.size() * 8, hipMemcpyDeviceToHost));
-    DM_CHECK(hipMemcpy(h2.data(), a.trace + 16384, h2.size() * 8, hipMemcpyDeviceToHost));
-    std::vector<double> col[12];
-    for (int s2 = 1; s2 + 1 < nst; ++s2) {
-      const unsigned long long* r = &h[(size_t)s2 * 8];
-      const unsigned long long* nx = &h[(size_t)(s2 + 1) * 8];
-      const unsigned long long* r2 = &h2[(size_t)s2 * 4];
-      col[0].push_back((double)(r[2] - r[1]));   // VALU phase 1
-      col[1].push_back((double)(r[3] - r[2]));   // VALU mid wait
-      col[2].push_back((double)(nx[0] - r[3]));  // VALU phase 2
-      col[3].push_back((double)(nx[1] - nx[0])); // VALU step-start wait
-      col[4].push_back((double)(r[6] - r[5]));   // MFMA phase 1
-      col[5].push_back((double)(r[7] - r[6]));
-      col[6].push_back((double)(nx[4] - r[7]));
-      col[7].push_back((double)(nx[5] - nx[4]));
-      col[8].push_back((double)(nx[0] - r[0]));  // whole step
-      if (r2[0] >= r[3] && r2[2] <= nx[0] && r2[0]) {
-        col[9].push_back((double)(r2[0] - r[3]));
-        col[10].push_back((double)(r2[2] - r2[0]));
-        col[11].push_back((double)(nx[0] - r2[2]));
-      }
-    }
-    auto med = [](std::vector<double> v) {
-      if (v.empty()) return 0.0;
-      std::sort(v.begin(), v.end());
-      return v[v.size() / 2];
-    };
-    const double tot = (double)(h[(size_t)(nst - 1) * 8] - h[8]) / (nst - 2);
-    fprintf(stderr,
-            "stem_bwd trace (medians, units/step; mean step %.0f): step %.0f | VALU p1 %.0f wait %.0f "
-            "p2 %.0f wait %.0f [p2: gather %.0f raw %.0f rest %.0f] | MFMA p1 %.0f wait %.0f p2 %.0f "
-            "wait %.0f\n",
-            tot, med(col[8]), med(col[0]), med(col[1]), med(col[2]), med(col[3]), med(col[9]),
-            med(col[10]), med(col[11]), med(col[4]), med(col[5]), med(col[6]), med(col[7]));
-  }
-
 }
 
 void stem_wcombine(const float* dslab, const float* gslab, int GD, const bf16_t* wk,

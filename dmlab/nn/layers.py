@@ -11,8 +11,6 @@ from __future__ import annotations
 import contextlib
 import math
 
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -234,7 +232,7 @@ class BasicBlock(Layer):
 
     def _down_stream(self):
         prog = getattr(self, "_prog", None)
-        if prog is None or os.environ.get("DMLAB_DOWN_FWD_STREAM", "1") == "0":
+        if prog is None:
             return None
         return prog._side_stream() if prog._native_active else None
 

@@ -427,9 +427,9 @@ class Program(nn.Module):
 
     def _aux_stream(self):
         """Third HIP stream, at the step stream's high priority, for critical-path work that
-        can run beside the main chain (a projection shortcut's BN backward); None when
-        disabled (``DMLAB_AUX_STREAM=0``) or without a side stream."""
-        if self._side_stream() is None or os.environ.get("DMLAB_AUX_STREAM", "1") == "0":
+        can run beside the main chain (a projection shortcut's BN backward); None without
+        a side stream (everything then runs serially on the step stream)."""
+        if self._side_stream() is None:
             return None
         dev = torch.cuda.current_device()
         key = ("aux", dev)

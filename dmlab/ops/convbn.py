@@ -42,6 +42,9 @@ _STEM_CFG = 60
 # The round-3 A/B switches (DMLAB_NO_PIPE / NO_RES64 / NO_FUSED_SKIP / NO_DGRAD_RED /
 # NO_WRES64 / WRES64_S / TAIL_WGRAD_FULL / WGRAD_BLOCKS / RES64_ADD_RED / STEM_CFG) are
 # settled and removed; their measurements stay in docs/KERNELS.md and profiles/.
+# So are round 6's (MERGE_SHORTCUT / MERGE_PIPE, RES64_RED_ADD, DOWN_FWD_STREAM, AUX_STREAM,
+# FIN_DIRECT, STEM_GRID / SPLIT / ABLATE / TRACE); docs/ARCHITECTURE.md lists the variables
+# that remain.
 
 
 def dgrad_cfg(M, cin, k, stride, cout, H=0, W=0):
@@ -502,11 +505,9 @@ _MULTI_IGEMM = (11, 12, 13, 14, 15, 16, 17)
 _MULTI_PIPE = (90, 91, 92, 93)
 # the layer-2 BN-backward apply folded into its halo consumers (DMLAB_BN_FOLD=1/0)
 _BN_FOLD_DEFAULT = "0"
-# DMLAB_RES64_RED_ADD default: layer-1 identity-block dgrads reduce the previous block's BN
-_RES64_RED_ADD_DEFAULT = "1"
 
 
-def _dgrad_red(L, red_for, cfg, stride, dx, allow_res64_add=False, complete_s2=False):
+def _dgrad_red(L, red_for, cfg, stride, dx, complete_s2=False):
     """conv_dgrad kwargs that reduce the consumer BN's backward sums in the dgrad epilogue
     (see convbn_bwd ``red_for``); {} when the kernel or the layer does not qualify.
 
@@ -535,13 +536,10 @@ def _dgrad_red(L, red_for, cfg, stride, dx, allow_res64_add=False, complete_s2=F
     # block's BN): round 3 measured them 0.3% slower per step (the add/mask epilogue cost the
     # kernel ~100 us, more than the contended pass it saved: profiles/
     # dgrad_bn_reduce_ab_r3s3.txt, red9); with the round-6 packed/bit-extract reduction they
-    # gain +0.26 % (profiles/res64_red_add_ab_r6.txt), default on; DMLAB_RES64_RED_ADD=0 opts
-    # out (``allow_res64_add``: tests).  The STEM's pooled-grid sums in the last layer-1 dgrad
-    # pay too: +0.5 % (the separate pooled reduce ran next to the full-CU tail weight gradient
+    # gained +0.26 % (profiles/res64_red_add_ab_r6.txt), so they reduce unconditionally (the
+    # opt-out switch was removed).  The STEM's pooled-grid sums in the last layer-1 dgrad
+    # paid too: +0.5 % (the separate pooled reduce ran next to the full-CU tail weight gradient
     # at ~2 TB/s; profiles/side_stream_sweep_r4f.txt)
-    if (cfg == 80 and mask is not None and not pool and not allow_res64_add
-            and os.environ.get("DMLAB_RES64_RED_ADD", _RES64_RED_ADD_DEFAULT) != "1"):
-        return {}
     N, H, W, C = dx.shape
     rows = (L.dgrad_s2_red_rows(N, H, W, cfg) if stride == 2
             else L.conv_stats_rows(N * H * W, cfg, C))
@@ -724,10 +722,8 @@ def convbn_bwd(layer, dout, ctx, need_dx, dx_add=None, dx_into=None, fused_skip=
             dx = empty_nhwc(N_, H, W, Cin, x)
             merge_kw = {}
             if (shortcut is not None and s == 2 and k == 3 and p == 1 and dx_add is None
-                    and (cfg in _MULTI_IGEMM
-                         or (cfg in _MULTI_PIPE and os.environ.get("DMLAB_MERGE_PIPE", "1") != "0"))
-                    and H % 2 == 0 and W % 2 == 0
-                    and os.environ.get("DMLAB_MERGE_SHORTCUT", "1") != "0"):
+                    and (cfg in _MULTI_IGEMM or cfg in _MULTI_PIPE)
+                    and H % 2 == 0 and W % 2 == 0):
                 dy2, wd2 = shortcut["join"]()
                 if (dy2.shape[:3] == dy.shape[:3] and dy2.shape[3] % 64 == 0
                         and (cfg in _MULTI_IGEMM or dy2.shape[3] == dy.shape[3])):

@@ -8,6 +8,7 @@ import torch.nn.functional as F
 
 from dmlab.models import ResNet18
 from dmlab.nn import cross_entropy
+from dmlab.nn.program import Program
 from dmlab.ops._native import lib
 
 pytestmark = pytest.mark.gpu
@@ -156,12 +157,14 @@ def test_resnet18_aux_stream_bit_identical(dev, monkeypatch):
     y = torch.randint(0, 10, (8,), device=dev)
     grads, stats = {}, {}
     for aux in ("1", "0"):
-        monkeypatch.setenv("DMLAB_AUX_STREAM", aux)
-        m = copy.deepcopy(base)
-        for _ in range(2):
-            m.zero_grad()
-            cross_entropy(m(x), y).backward()
-        torch.cuda.synchronize()
+        with monkeypatch.context() as mp:  # undone after each run: the order does not matter
+            if aux == "0":  # the serial order: no aux stream
+                mp.setattr(Program, "_aux_stream", lambda self: None)
+            m = copy.deepcopy(base)
+            for _ in range(2):
+                m.zero_grad()
+                cross_entropy(m(x), y).backward()
+            torch.cuda.synchronize()
         grads[aux] = [p.grad.clone() for p in m.parameters()]
         stats[aux] = [b.clone() for b in m.buffers()]
     for ga, gb in zip(grads["1"], grads["0"]):

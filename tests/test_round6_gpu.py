@@ -146,10 +146,11 @@ def _rel(a, b):
 @pytest.mark.parametrize("merge", ["1", "0"])
 def test_resnet18_step_merged_shortcut(dev, merge, monkeypatch):
     """A whole native ResNet-18 step with the merged projection data gradients (and their
-    reduction epilogues) on and off: held to the error level of PyTorch's bf16 autocast against
-    the fp32 step, per parameter (the criterion of test_resnet18_native_matches_reference), and
-    the merged launches are really taken (layers 2-3 on igemm tiles; layer 4's pipelined tile
-    keeps the separate launch)."""
+    reduction epilogues) and with the two-launch path that shapes which cannot merge still take
+    (selected here by emptying the lists of merging tiles): held to the error level of PyTorch's
+    bf16 autocast against the fp32 step, per parameter (the criterion of
+    test_resnet18_native_matches_reference), and the merged launches are really taken (layers
+    2-3 on igemm tiles, layer 4 on a pipelined tile, cfg 90-93)."""
     import copy
 
     import torch.nn.functional as F
@@ -158,7 +159,9 @@ def test_resnet18_step_merged_shortcut(dev, merge, monkeypatch):
     from dmlab.nn import cross_entropy
     from dmlab.ops import _native
 
-    monkeypatch.setenv("DMLAB_MERGE_SHORTCUT", merge)
+    if merge == "0":
+        monkeypatch.setattr("dmlab.ops.convbn._MULTI_IGEMM", ())
+        monkeypatch.setattr("dmlab.ops.convbn._MULTI_PIPE", ())
     L = _native.lib()
     calls = []
 
@@ -169,7 +172,8 @@ def test_resnet18_step_merged_shortcut(dev, merge, monkeypatch):
                 return f
 
             def wrapped(*a, **k):
-                calls.append(("dy2" in k, "red_y" in k, a[5] if len(a) > 5 else k.get("stride")))
+                calls.append(("dy2" in k, "red_y" in k, a[5] if len(a) > 5 else k.get("stride"),
+                              a[8] if len(a) > 8 else k.get("cfg")))
                 return f(*a, **k)
             return wrapped
 
@@ -202,6 +206,7 @@ def test_resnet18_step_merged_shortcut(dev, merge, monkeypatch):
     s2 = [c_ for c_ in calls if c_[2] == 2]
     if merge == "1":
         assert len(merged) >= 1 and all(m[1] for m in merged), calls
+        assert any(90 <= m[3] <= 93 for m in merged), calls
     else:
         assert not merged and s2, calls
 
