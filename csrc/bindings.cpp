@@ -85,6 +85,80 @@ void rows_mean(at::Tensor x, at::Tensor out, double scale) {
                 (float)scale, cur_stream());
 }
 
+// ------------------------------------------------------------------ LARS (csrc/lars.hip)
+// Build the segment and chunk tables for tensors at `offsets` (elements, 16-B aligned) with
+// `numels` elements each inside a flat buffer of `total` elements.  Returns CPU int64 tensors
+// (seg [n,5], chunks [m,3]); the caller moves them to the device once.  Everything the kernels
+// index with is validated here, on the host.
+std::vector<at::Tensor> lars_table(std::vector<int64_t> offsets, std::vector<int64_t> numels,
+                                   std::vector<bool> adapted, int64_t total) {
+  const size_t n = offsets.size();
+  TORCH_CHECK(numels.size() == n && adapted.size() == n, "lars_table: list lengths differ");
+  TORCH_CHECK(n < (size_t)1 << 30, "lars_table: too many tensors");
+  const int64_t C = dm::lars_chunk();
+  int64_t m = 0;
+  for (size_t t = 0; t < n; ++t) {
+    TORCH_CHECK(offsets[t] >= 0 && numels[t] >= 0 && offsets[t] + numels[t] <= total,
+                "lars_table: tensor ", t, " lies outside the flat buffer");
+    TORCH_CHECK(offsets[t] % 4 == 0, "lars_table: tensor ", t, " is not 16-B aligned");
+    for (size_t u = 0; u < t; ++u)
+      TORCH_CHECK(offsets[u] + numels[u] <= offsets[t] || offsets[t] + numels[t] <= offsets[u],
+                  "lars_table: tensors ", u, " and ", t, " overlap");
+    m += (numels[t] + C - 1) / C;
+  }
+  TORCH_CHECK(m < (int64_t)1 << 30, "lars_table: too many chunks");
+  auto opt = at::TensorOptions().dtype(at::kLong);
+  at::Tensor seg = at::empty({(int64_t)n, 5}, opt), chunks = at::empty({m, 3}, opt);
+  int64_t* sp = seg.data_ptr<int64_t>();
+  int64_t* cp = chunks.data_ptr<int64_t>();
+  int64_t c = 0;
+  for (size_t t = 0; t < n; ++t) {
+    const int64_t cnt = (numels[t] + C - 1) / C;
+    sp[5 * t + 0] = offsets[t];
+    sp[5 * t + 1] = numels[t];
+    sp[5 * t + 2] = adapted[t] ? 1 : 0;
+    sp[5 * t + 3] = c;
+    sp[5 * t + 4] = cnt;
+    for (int64_t i = 0; i < cnt; ++i, ++c) {
+      cp[3 * c + 0] = offsets[t] + i * C;
+      cp[3 * c + 1] = std::min(C, numels[t] - i * C);
+      cp[3 * c + 2] = (int64_t)t;
+    }
+  }
+  return {seg, chunks};
+}
+
+void lars_step(at::Tensor w, at::Tensor g, at::Tensor buf, at::Tensor seg, at::Tensor chunks,
+               at::Tensor hyper, at::Tensor partial, at::Tensor tot, at::Tensor stats,
+               at::Tensor gnorm, bool nesterov, int64_t launches) {
+  for (auto* t : {&w, &g, &buf, &hyper, &partial, &tot, &stats, &gnorm}) {
+    CHECK_CUDA(*t); CHECK_F32(*t); CHECK_CONTIG(*t); CHECK_ALIGN16(*t);
+    TORCH_CHECK(t->device() == w.device(), "lars_step: tensors on different devices");
+  }
+  for (auto* t : {&seg, &chunks}) {
+    CHECK_CUDA(*t); CHECK_CONTIG(*t);
+    TORCH_CHECK(t->scalar_type() == at::kLong && t->dim() == 2 && t->device() == w.device(),
+                "lars_step: tables are 2-D int64 tensors on the parameters' device");
+  }
+  TORCH_CHECK(g.numel() == w.numel() && buf.numel() == w.numel(), "param/grad/buf size mismatch");
+  TORCH_CHECK(seg.size(1) == 5 && chunks.size(1) == 3, "lars_step: seg [n,5], chunks [m,3]");
+  const int64_t n = seg.size(0), m = chunks.size(0);
+  TORCH_CHECK(n < ((int64_t)1 << 30) && m < ((int64_t)1 << 30), "lars_step: table too large");
+  TORCH_CHECK(hyper.numel() == dm::lars_hyper_count(), "lars_step: hyper holds ",
+              dm::lars_hyper_count(), " floats");
+  TORCH_CHECK(partial.numel() == 2 * m && tot.numel() == 2 * n && stats.numel() == 3 * n &&
+                  gnorm.numel() == 1,
+              "lars_step: workspace sizes do not match the tables");
+  TORCH_CHECK(launches >= 1 && launches <= 7, "lars_step: launches is a mask of bits 0..2");
+  const DeviceGuard guard(w.device());
+  dm::lars_step(w.data_ptr<float>(), g.data_ptr<float>(), buf.data_ptr<float>(), w.numel(),
+                reinterpret_cast<const long long*>(seg.data_ptr<int64_t>()), (int)n,
+                reinterpret_cast<const long long*>(chunks.data_ptr<int64_t>()), (int)m,
+                hyper.data_ptr<float>(), partial.data_ptr<float>(), tot.data_ptr<float>(),
+                stats.data_ptr<float>(), gnorm.data_ptr<float>(), nesterov, (int)launches,
+                cur_stream());
+}
+
 // ------------------------------------------------------------------ small conv (LeNet)
 inline bool is_bf16(const at::Tensor& t) { return t.scalar_type() == at::kBFloat16; }
 inline void check_act(const at::Tensor& t, const char* n) {
@@ -427,6 +501,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_step", &adam_step, "fused flat Adam step");
   m.def("cast_f32_bf16", &cast_f32_bf16, "fp32 -> bf16 cast");
   m.def("rows_mean", &rows_mean, "[rows,N] -> [N] scaled row sum");
+  m.def("lars_chunk", &dm::lars_chunk, "elements per LARS chunk (compile-time constant)");
+  m.def("lars_table", &lars_table, "host-validated LARS segment/chunk tables (CPU int64)",
+        py::arg("offsets"), py::arg("numels"), py::arg("adapted"), py::arg("total"));
+  m.def("lars_step", &lars_step, "fused flat LARS step (3 launches)", py::arg("w"),
+        py::arg("g"), py::arg("buf"), py::arg("seg"), py::arg("chunks"), py::arg("hyper"),
+        py::arg("partial"), py::arg("tot"), py::arg("stats"), py::arg("gnorm"),
+        py::arg("nesterov"), py::arg("launches") = 7);
   m.def("conv_small_fwd", &conv_small_fwd);
   m.def("conv_small_bwd", &conv_small_bwd);
   m.def("conv_small_workspace", &conv_small_workspace);

@@ -18,6 +18,20 @@ void cast_f32_bf16(const float* x, bf16_t* y, long long n, hipStream_t st);
 void rows_mean(const float* x, float* out, int rows, long long n, float scale,
                hipStream_t st);
 
+// lars.hip: fused LARS step over the flat buffers (3 launches).  seg [n_tensors,5] and
+// chunks [n_chunks,3] are the int64 device tables described there; hyper holds
+// lars_hyper_count() floats (lr, momentum, weight decay, trust coefficient, eps,
+// grad_scale, max_grad_norm or <= 0); partial [n_chunks,2] and tot [n_tensors,2] are
+// workspaces; stats [n_tensors,3] and gnorm [1] are outputs.
+// launches: bit 0 partial sums, bit 1 per-tensor totals, bit 2 update (7 = the step; a subset only
+// to time the launches one by one, tools/bench_optim.py).
+int lars_chunk();
+int lars_hyper_count();
+void lars_step(float* w, const float* g, float* buf, long long total, const long long* seg,
+               int n_tensors, const long long* chunks, int n_chunks, const float* hyper,
+               float* partial, float* tot, float* stats, float* gnorm, bool nesterov,
+               int launches, hipStream_t st);
+
 }  // namespace dm
 
 namespace dm {

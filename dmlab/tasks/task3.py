@@ -23,7 +23,7 @@ import torch
 from dmlab.data import DeviceLoader, MySampler, load_mnist
 from dmlab.models import Net, ResNet18
 from dmlab.nn import CrossEntropyLoss
-from dmlab.optim import SGD
+from dmlab.optim import LARS, SGD, WarmupPolyLR
 from dmlab.parallel import DDP, comm, env
 from dmlab.tasks.common import test, train
 
@@ -54,6 +54,14 @@ def parse_args(argv=None):
     p.add_argument("--epochs", type=int, default=2)
     p.add_argument("--lr", type=float, default=0.001)
     p.add_argument("--momentum", type=float, default=0.9)
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
+                   help="lars: layer-wise adaptive rate scaling (large batches); BN parameters "
+                        "and biases are neither adapted nor decayed")
+    p.add_argument("--weight-decay", type=float, default=0.0)
+    p.add_argument("--trust-coef", type=float, default=0.001, help="LARS trust coefficient")
+    p.add_argument("--warmup-steps", type=int, default=0,
+                   help="> 0: linear warm-up over this many steps, then polynomial (power 2) "
+                        "decay to 0 at the last step; 0 keeps --lr constant")
     p.add_argument("--bucket-mb", type=float, default=25.0)
     p.add_argument("--allreduce", default="auto", choices=["auto", "rccl", "xgmi"],
                    help="small-bucket all-reduce: RCCL ring or the one-shot xGMI kernel.  At "
@@ -86,6 +94,10 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
+    if a.fused == "1" and (a.optimizer != "sgd" or a.warmup_steps > 0):
+        raise SystemExit("--fused 1 runs constant-rate SGD inside the fused LeNet step; "
+                         "--optimizer lars and --warmup-steps need the layer-wise loop "
+                         "(--fused auto or 0)")
     dev = env.init(a.n_devices, a.rank, a.master_addr, a.master_port, backend=a.backend,
                    device_type=a.device)
     rank, ws = env.get_rank(), env.get_world_size()
@@ -133,7 +145,12 @@ def main(argv=None):
     act = torch.bfloat16 if (a.dtype == "bf16" and a.model == "lenet" and dev.type == "cuda") \
         else None
     loader = DeviceLoader(train_set.to(dev, dtype=act), a.batch_size, sampler=sampler)
-    opt = SGD(model.parameters(), lr=a.lr, momentum=a.momentum)
+    if a.optimizer == "lars":
+        opt = LARS(model.parameters(), lr=a.lr, momentum=a.momentum,
+                   weight_decay=a.weight_decay, trust_coefficient=a.trust_coef)
+    else:
+        opt = SGD(model.parameters(), lr=a.lr, momentum=a.momentum,
+                  weight_decay=a.weight_decay)
     if a.resume:
         from dmlab.utils import checkpoint
 
@@ -148,7 +165,8 @@ def main(argv=None):
         net = model
         agg = comm.GradAggregator(model, "allreduce", timing="events")
     fused = a.fused == "1" or (a.fused == "auto" and a.model == "lenet" and dev.type == "cuda"
-                               and a.dp == "ddp")
+                               and a.dp == "ddp" and a.optimizer == "sgd"
+                               and a.warmup_steps == 0)
     if fused:
         if a.model != "lenet" or dev.type != "cuda" or a.dp != "ddp":
             raise SystemExit("--fused 1 needs --model lenet on a GPU with --dp ddp")
@@ -162,8 +180,18 @@ def main(argv=None):
                             graph_steps=a.graph_steps, max_steps=a.max_steps)
         stats.update(fused=True, hip_graph=graph, hip_graph_steps=stats.pop("graph_steps"))
     else:
+        after_step = None
+        if a.warmup_steps > 0:  # the schedule sets the rate of step t+1 after step t
+            opt.lr = a.lr  # a resumed run restarts the schedule from its base rate
+            total = a.epochs * len(loader)
+            if a.max_steps is not None:
+                total = min(total, a.max_steps)
+            sched = WarmupPolyLR(opt, min(a.warmup_steps, total), total)
+            after_step = lambda _step: sched.step()  # noqa: E731
         stats = train(net, loader, CrossEntropyLoss(), opt, a.epochs, rank=rank, aggregate=agg,
-                      batch_size=a.batch_size, max_steps=a.max_steps)
+                      batch_size=a.batch_size, max_steps=a.max_steps, after_step=after_step)
+    if a.optimizer != "sgd":
+        stats["optimizer"] = a.optimizer
     print("Training time: {}".format(stats["train_time"]))
     if rank == 0:
         print("Throughput: {:.1f} samples/s (whole job, {} rank{})".format(
