@@ -65,9 +65,9 @@ const unsigned char* bit_mask(const c10::optional<at::Tensor>& m, const at::Tens
   return m->data_ptr<uint8_t>();
 }
 
-// The folded BatchNorm-backward operand (kernels.h BnBwdIn) of a data / weight gradient whose
-// dY argument is that BN's OUTPUT gradient dz: y (its input, dz's shape), coef [3][C] (bn_backward
-// with dy None), scale/shift (ReLU mask from y) or the 1-bit mask, neither: no ReLU
+// The folded BatchNorm-backward operand (kernels.h BnBwdIn) of a weight gradient whose dY
+// argument is that BN's OUTPUT gradient dz: y (its input, dz's shape), coef [3][C] (a, b, c of
+// dy = a*dz' + b*y + c), scale/shift (ReLU mask from y) or the 1-bit mask, neither: no ReLU
 dm::BnBwdIn bwd_in(const at::Tensor& dz, const at::Tensor& y, const at::Tensor& coef,
                    const c10::optional<at::Tensor>& sc, const c10::optional<at::Tensor>& sh,
                    const c10::optional<at::Tensor>& mask) {
@@ -141,31 +141,6 @@ void conv_fwd(at::Tensor x, at::Tensor wpack, at::Tensor y, c10::optional<at::Te
   dm::igemm_fwd(bp(x), bp(wpack), bp(y), ap, sp, g, cfg, cur_stream());
 }
 
-// statistics rows a forward conv of this cfg writes (one per row tile, or per workgroup of the
-// persistent cfg 80); ncols is unused
-// The BN-backward apply of a 3x3/s1/p1 conv's BatchNorm can fold into both consumers: the data
-// gradient on the cfg 42 halo tile and the 9-tap halo weight gradient (conv_dgrad / conv_wgrad
-// bwd_*).  x: the conv's input [N,H,W,Cin]; Cout its output channels.
-bool bn_fold_supported(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
-  if (Cin % 64 || Cout % 64 || ((Cout / 8) & (Cout / 8 - 1)) || ((Cin / 8) & (Cin / 8 - 1)))
-    return false;
-  dm::ConvGeom d{};  // data gradient (conv_dgrad stride 1)
-  d.N = N; d.H = H; d.W = W; d.C = Cout; d.lgC8 = ilog2(Cout / 8);
-  d.OH = H; d.OW = W; d.OC = Cin; d.KW = 3; d.Ncols = Cin; d.wK = 9 * Cout;
-  d.Hg = H; d.Wg = W; d.isy = 1; d.isx = 1; d.osy = 1; d.osx = 1; d.oy0 = 0; d.ox0 = 0;
-  d.nth = 3; d.ntw = 3; d.dy0 = 1; d.dys = -1; d.dx0 = 1; d.dxs = -1;
-  d.kh0 = 0; d.khs = 1; d.kw0 = 0; d.kws = 1; d.M = N * H * W; d.K = 9 * Cout;
-  dm::geom_finalize(d);
-  dm::ConvGeom w{};  // weight gradient (fwd_geom of the conv)
-  w.N = N; w.H = H; w.W = W; w.C = Cin; w.lgC8 = ilog2(Cin / 8);
-  w.Hg = H; w.Wg = W; w.isy = 1; w.isx = 1; w.OH = H; w.OW = W; w.OC = Cout;
-  w.osy = 1; w.osx = 1; w.oy0 = 0; w.ox0 = 0; w.nth = 3; w.ntw = 3; w.dy0 = -1; w.dys = 1;
-  w.dx0 = -1; w.dxs = 1; w.kh0 = 0; w.khs = 1; w.kw0 = 0; w.kws = 1; w.KW = 3;
-  w.Ncols = Cout; w.wK = 9 * Cin; w.M = N * H * W; w.K = 9 * Cin;
-  dm::geom_finalize(w);
-  return dm::conv_halo_supported(d) && dm::wgrad_halo_supported(w);
-}
-
 // part rows of a stride-2 data gradient with the reduction epilogue (conv_dgrad red_part)
 int64_t dgrad_s2_red_rows(int64_t N, int64_t H, int64_t W, int64_t cfg) {
   dm::ConvGeomSet set{};
@@ -179,6 +154,8 @@ int64_t dgrad_s2_red_rows(int64_t N, int64_t H, int64_t W, int64_t cfg) {
   return dm::igemm_multi_rows(set, ng, (int)cfg);
 }
 
+// statistics rows a forward conv of this cfg writes (one per row tile, or per workgroup of the
+// persistent cfg 80); ncols is unused
 int64_t conv_stats_rows(int64_t M, int64_t cfg, int64_t ncols) {
   if (cfg == 80) return dm::res64_grid(M);
   const int bm = dm::igemm_fwd_rowtile(cfg);
@@ -193,12 +170,7 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
                 c10::optional<at::Tensor> red_scale, c10::optional<at::Tensor> red_shift,
                 c10::optional<at::Tensor> red_mean, c10::optional<at::Tensor> red_invstd,
                 c10::optional<at::Tensor> red_part, c10::optional<at::Tensor> red_mask,
-                c10::optional<at::Tensor> dy2, c10::optional<at::Tensor> wd2,
-                c10::optional<at::Tensor> bwd_y, c10::optional<at::Tensor> bwd_coef,
-                c10::optional<at::Tensor> bwd_scale, c10::optional<at::Tensor> bwd_shift,
-                c10::optional<at::Tensor> bwd_mask) {
-  // bwd_* (optional, stride 1, cfg 42): dy is a BatchNorm's OUTPUT gradient; the kernel stages
-  // that BN's backward a*dz' + b*y + c itself (bwd_in)
+                c10::optional<at::Tensor> dy2, c10::optional<at::Tensor> wd2) {
   // dy2 / wd2 (optional, stride 2): a 1x1/s2/p0 projection's output gradient and packed data-
   // gradient weights [Cin][1][1][C2]; its data gradient is merged into this launch (parity
   // class (0,0) gets a second K segment), so dx is written once, complete
@@ -248,13 +220,6 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
     return dm::BnBwdRed{bp(*red_y), bit_mask(red_mask, dx, "red_mask"), fp(*red_scale),
                         fp(*red_shift), fp(*red_mean), fp(*red_invstd), fp(*red_part)};
   };
-  dm::BnBwdIn bwd{};
-  const bool has_bwd = bwd_y.has_value();
-  if (has_bwd) {
-    TORCH_CHECK(stride == 1 && cfg == 42 && bwd_coef.has_value(),
-                "bwd_*: a stride-1 cfg 42 (halo) data gradient with bwd_coef");
-    bwd = bwd_in(dy, *bwd_y, *bwd_coef, bwd_scale, bwd_shift, bwd_mask);
-  }
   if (stride == 1) {
     auto g = base;
     g.addm = addm;
@@ -263,11 +228,6 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
     g.kh0 = 0; g.khs = 1; g.kw0 = 0; g.kws = 1;
     g.M = (long long)N * H * W; g.K = KH * KW * Cout;
     dm::geom_finalize(g);
-    if (has_bwd) {
-      int hbn = 0, hwv = 0;
-      TORCH_CHECK(dm::halo_cfg((int)cfg, hbn, hwv) && dm::conv_halo_supported(g),
-                  "bwd_*: the geometry must suit the halo kernel");
-    }
     if (red_y.has_value()) {
       const bool pipe = cfg >= 90 && cfg <= 93 && dm::conv_pipe_supported(g, (int)cfg);
       int hbn = 0, hwv = 0;
@@ -278,23 +238,14 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
       if (pipe)
         dm::conv_pipe(bp(dy), bp(wd), bp(dx), addp, nullptr, g, (int)cfg, st, &red);
       else if (halo)
-        dm::conv_halo(bp(dy), bp(wd), bp(dx), addp, nullptr, g, hbn, hwv, st, nullptr, nullptr, &red,
-                      has_bwd ? &bwd : nullptr);
+        dm::conv_halo(bp(dy), bp(wd), bp(dx), addp, nullptr, g, hbn, hwv, st, nullptr, nullptr, &red);
       else
         dm::conv_res64(bp(dy), bp(wd), bp(dx), addp, nullptr, g, st, nullptr, nullptr, &red);
-      return;
-    }
-    if (has_bwd) {
-      int hbn = 0, hwv = 0;
-      dm::halo_cfg((int)cfg, hbn, hwv);
-      dm::conv_halo(bp(dy), bp(wd), bp(dx), addp, nullptr, g, hbn, hwv, st, nullptr, nullptr, nullptr,
-                    &bwd);
       return;
     }
     dm::igemm_fwd(bp(dy), bp(wd), bp(dx), addp, nullptr, g, cfg, st);
     return;
   }
-  TORCH_CHECK(!has_bwd, "bwd_*: stride-1 data gradients only");
   // parity classes write disjoint output pixels; a class with no taps (e.g. the odd
   // pixels of a 1x1/s2 conv) is exactly zero, so zero-fill once up front when needed
   bool any_empty = false;
@@ -615,19 +566,12 @@ void bn_backward(c10::optional<at::Tensor> dout, c10::optional<at::Tensor> out, 
                  at::Tensor dbeta, double gbeta, int64_t mode, c10::optional<at::Tensor> scale,
                  c10::optional<at::Tensor> shift, c10::optional<at::Tensor> pdy,
                  c10::optional<at::Tensor> pidx, int64_t K, int64_t S, int64_t P,
-                 c10::optional<at::Tensor> dy, c10::optional<at::Tensor> dres, at::Tensor work,
+                 at::Tensor dy, c10::optional<at::Tensor> dres, at::Tensor work,
                  c10::optional<at::Tensor> pre_slab, int64_t pre_rows,
                  c10::optional<at::Tensor> mask) {
-  // dy None: reduce + finalize only -- dgamma/dbeta and the coefficients a, b, cc of
-  // dy = a*dz + b*y + cc are left in work (bn_bwd_coef_offset) for a consumer kernel that
-  // applies them while staging its operand (conv_dgrad / conv_wgrad bwd_*)
   need_bf16_nhwc(y, "y");
-  if (dy.has_value()) {
-    need_bf16_nhwc(*dy, "dy");
-    TORCH_CHECK(dy->sizes() == y.sizes());
-  } else {
-    TORCH_CHECK(!dres.has_value() && mode != 3, "dy None: no residual gradient, no pool mode");
-  }
+  need_bf16_nhwc(dy, "dy");
+  TORCH_CHECK(dy.sizes() == y.sizes());
   TORCH_CHECK(mode >= 0 && mode <= 4);
   const int C = y.size(3);
   TORCH_CHECK(C % 8 == 0 && 256 % (C / 8) == 0, "bn_backward: C/8 must divide 256");
@@ -684,7 +628,7 @@ void bn_backward(c10::optional<at::Tensor> dout, c10::optional<at::Tensor> out, 
   const DeviceGuard guard(y.device());
   dm::bn_backward(doutp, outp, bp(y), fp(mean), fp(invstd), fp(gamma), fp(dgamma), fp(dbeta),
                   (float)gbeta, M, C, (int)mode, scp, shp, pdyp, pidxp, y.size(1), y.size(2), OH,
-                  OW, K, S, P, dy.has_value() ? bp(*dy) : nullptr, drp, fp(work), cur_stream(), pre_slab.has_value() ? fp(*pre_slab) : nullptr,
+                  OW, K, S, P, bp(dy), drp, fp(work), cur_stream(), pre_slab.has_value() ? fp(*pre_slab) : nullptr,
                   (int)pre_rows, mp);
 }
 
@@ -711,11 +655,6 @@ void bn_relu_maxpool(at::Tensor y, at::Tensor scale, at::Tensor shift, at::Tenso
 }
 
 int64_t bn_bwd_rows(int64_t M, int64_t C) { return dm::bn_bwd_groups(M, C); }
-
-// element offset of the [3][C] backward coefficients in bn_backward's work buffer
-int64_t bn_bwd_coef_offset(int64_t M, int64_t C, bool pre_sums) {
-  return pre_sums ? 0 : (int64_t)dm::bn_bwd_groups(M, C) * 2 * C;
-}
 
 // Σdz, Σdz·x̂ partials of (dout masked by y*scale+shift > 0) -> part [rows][2C]; returns rows
 int64_t bn_bwd_reduce_masked(at::Tensor dout, at::Tensor y, at::Tensor mean, at::Tensor invstd,
@@ -935,10 +874,7 @@ void register_resnet(pybind11::module_& m) {
         py::arg("red_shift") = py::none(), py::arg("red_mean") = py::none(),
         py::arg("red_invstd") = py::none(), py::arg("red_part") = py::none(),
         py::arg("red_mask") = py::none(), py::arg("dy2") = py::none(),
-        py::arg("wd2") = py::none(), py::arg("bwd_y") = py::none(),
-        py::arg("bwd_coef") = py::none(), py::arg("bwd_scale") = py::none(),
-        py::arg("bwd_shift") = py::none(), py::arg("bwd_mask") = py::none());
-  m.def("bn_fold_supported", &bn_fold_supported);
+        py::arg("wd2") = py::none());
   m.def("dgrad_s2_red_rows", &dgrad_s2_red_rows, py::arg("N"), py::arg("H"), py::arg("W"),
         py::arg("cfg"));
   m.def("conv_wgrad", &conv_wgrad, py::arg("x"), py::arg("dy"), py::arg("dw"), py::arg("slab"),
@@ -971,7 +907,6 @@ void register_resnet(pybind11::module_& m) {
         py::arg("out"), py::arg("idx"), py::arg("K"), py::arg("S"), py::arg("P"),
         py::arg("yarg") = py::none());
   m.def("bn_bwd_rows", &bn_bwd_rows);
-  m.def("bn_bwd_coef_offset", &bn_bwd_coef_offset);
   m.def("bn_bwd_reduce_masked", &bn_bwd_reduce_masked);
   m.def("maxpool_fwd", &maxpool_fwd);
   m.def("maxpool_bwd", &maxpool_bwd);

@@ -1220,7 +1220,7 @@ void bn_backward(const bf16_t* dout, const bf16_t* out, const bf16_t* y, const f
   else
     bn_bwd_finalize_kernel<256, FIN_CH><<<(C + FIN_CH - 1) / FIN_CH, 256, 0, st>>>(fin, rows, C,
                                                                             (double)M, fb);
-  if (!dy) return;  // coefficients only (a consumer kernel applies dy = a·dz + b·y + c itself)
+  if (!dy) return;  // coefficients only: stem_bwd_fused / stem_bwd_fused2 apply dy themselves
   const long long n8 = M * C / 8;
   // grid-strided mode 3: workgroup cap 4096 (1024-8192 within noise,
   // profiles/bn_bwd_apply_grid_ab_r3s3.txt)

@@ -146,13 +146,14 @@ struct BnBwdRed {
   const float* is;
   float* part;
 };
-// The BatchNorm backward apply folded into a consumer's operand staging (the data and weight
-// gradients of the conv that produced that BN's input): the staged operand is the BN's OUTPUT
-// gradient dz, and the kernel stages dy = a*dz' + b*y + c (dz' = dz where the ReLU passed:
-// y*sc + sh > 0 when sc is set, bit j of the 1-bit mask when mask is set, everywhere when
-// neither) instead of reading a materialised dy.  coef: [3][C] a, b, c (bn_backward, dy None).
+// The BatchNorm backward apply folded into the 9-tap halo weight gradient's dY staging (the conv
+// that produced that BN's input): the staged operand is the BN's OUTPUT gradient dz, and the
+// kernel stages dy = a*dz' + b*y + c (dz' = dz where the ReLU passed: y*sc + sh > 0 when sc is
+// set, bit j of the 1-bit mask when mask is set, everywhere when neither) instead of reading a
+// materialised dy.  coef: [3][C] a, b, c.  No model path uses it (measured slower,
+// docs/KERNELS.md).
 // Every pointer is valid (sc / sh alias coef when unused) and `mode` says which mask applies
-// (0: none, 2: y*sc + sh > 0, 4: the 1-bit mask), so the kernels load unconditionally: a load
+// (0: none, 2: y*sc + sh > 0, 4: the 1-bit mask), so the kernel loads unconditionally: a load
 // under a branch leaves a phi that makes the compiler drain every prefetch in flight.
 struct BnBwdIn {
   const bf16_t* y;
@@ -183,7 +184,7 @@ bool halo_cfg(int cfg, int& bn, int& waves);
 void conv_halo(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
                const ConvGeom& g, int bn, int waves, hipStream_t st,
                const float* pre_sc = nullptr, const float* pre_sh = nullptr,
-               const BnBwdRed* red = nullptr, const BnBwdIn* bwd = nullptr);
+               const BnBwdRed* red = nullptr);
 bool wgrad_halo_supported(const ConvGeom& g);
 // stride-2 3x3 weight gradient over the four input parity planes (wgrad cfg 7)
 bool wgrad_s2_supported(const ConvGeom& g);
