@@ -393,6 +393,50 @@ void argmax_count(at::Tensor logits, at::Tensor labels, at::Tensor correct) {
                    (unsigned long long*)correct.data_ptr(), is_bf16(logits), cur_stream());
 }
 
+void cross_entropy_smooth(at::Tensor logits, at::Tensor labels, at::Tensor rowloss, at::Tensor loss,
+                          c10::optional<at::Tensor> dlogits, double scale, double eps) {
+  check_act(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && labels.scalar_type() == at::kLong && labels.numel() == logits.size(0));
+  TORCH_CHECK(labels.is_cuda() && labels.is_contiguous(), "labels: contiguous device tensor");
+  TORCH_CHECK(eps >= 0.0 && eps <= 1.0, "label smoothing must be in [0, 1]");
+  TORCH_CHECK(logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(0) < (1ll << 31) &&
+              logits.size(1) < (1ll << 31), "logits: empty or too large");
+  TORCH_CHECK(rowloss.is_cuda() && rowloss.is_contiguous(), "rowloss: contiguous device tensor");
+  CHECK_F32(rowloss); CHECK_F32(loss);
+  TORCH_CHECK(rowloss.numel() >= logits.size(0) && loss.numel() >= 1);
+  if (dlogits.has_value()) { check_act(*dlogits, "dlogits"); TORCH_CHECK(dlogits->sizes() == logits.sizes() && is_bf16(*dlogits) == is_bf16(logits)); }
+  const DeviceGuard guard(logits.device());
+  dm::cross_entropy_smooth(logits.data_ptr(), (const long long*)labels.data_ptr(),
+                           rowloss.data_ptr<float>(), loss.data_ptr<float>(),
+                           dlogits.has_value() ? dlogits->data_ptr() : nullptr, logits.size(0),
+                           logits.size(1), (float)scale, (float)eps, -100, is_bf16(logits),
+                           cur_stream());
+}
+
+// counts: int64[3] = {n, top-1 hits, top-k hits}; loss: float64[1]; both accumulate
+void eval_metrics(at::Tensor logits, at::Tensor labels, at::Tensor rowloss, at::Tensor rowrank,
+                  int64_t k, at::Tensor counts, at::Tensor loss) {
+  check_act(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && labels.scalar_type() == at::kLong && labels.numel() == logits.size(0));
+  TORCH_CHECK(labels.is_cuda() && labels.is_contiguous(), "labels: contiguous device tensor");
+  TORCH_CHECK(logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(0) < (1ll << 31) &&
+              logits.size(1) < (1ll << 31), "logits: empty or too large");
+  TORCH_CHECK(rowloss.is_cuda() && rowloss.is_contiguous(), "rowloss: contiguous device tensor");
+  TORCH_CHECK(k >= 1 && k < 0x7fffffff, "k must be >= 1");
+  CHECK_F32(rowloss);
+  TORCH_CHECK(rowrank.is_cuda() && rowrank.is_contiguous() && rowrank.scalar_type() == at::kInt);
+  TORCH_CHECK(rowloss.numel() >= logits.size(0) && rowrank.numel() >= logits.size(0));
+  TORCH_CHECK(counts.is_cuda() && counts.is_contiguous() && counts.scalar_type() == at::kLong &&
+              counts.numel() >= 3, "counts: int64[3]");
+  TORCH_CHECK(loss.is_cuda() && loss.is_contiguous() && loss.scalar_type() == at::kDouble &&
+              loss.numel() >= 1, "loss: float64[1]");
+  const DeviceGuard guard(logits.device());
+  dm::eval_metrics(logits.data_ptr(), (const long long*)labels.data_ptr(), rowloss.data_ptr<float>(),
+                   rowrank.data_ptr<int>(), logits.size(0), logits.size(1), (int)k,
+                   (long long*)counts.data_ptr(), loss.data_ptr<double>(), is_bf16(logits),
+                   cur_stream());
+}
+
 void spin_us(double us) { dm::spin_us(us, cur_stream()); }
 
 // One LeNet training step (csrc/lenet_fused.hip).  w: conv1.w, conv1.b, conv2.w, conv2.b,
@@ -531,6 +575,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("p2p_xgmi_recv", &p2p_xgmi_recv);
   m.def("cross_entropy", &cross_entropy);
   m.def("argmax_count", &argmax_count);
+  m.def("cross_entropy_smooth", &cross_entropy_smooth);
+  m.def("eval_metrics", &eval_metrics);
   m.def("spin_us", &spin_us);
   m.def("lenet_fused_step", &lenet_fused_step, "one fused LeNet training step (2 dispatches)",
         py::arg("x"), py::arg("labels"), py::arg("w"), py::arg("rec"), py::arg("cslab"),

@@ -59,6 +59,14 @@ void cross_entropy(const void* logits, const long long* labels, float* rowloss, 
                    hipStream_t st);
 void argmax_count(const void* logits, const long long* labels, int B, int C,
                   unsigned long long* correct, bool bf16, hipStream_t st);
+// label-smoothed cross-entropy (eps in [0, 1]); same two launches as cross_entropy
+void cross_entropy_smooth(const void* logits, const long long* labels, float* rowloss, float* loss,
+                          void* dlogits, int B, int C, float scale, float eps, int ignore_index,
+                          bool bf16, hipStream_t st);
+// per-row NLL + label rank (B floats / B ints of scratch), then counts[3] = {n, top-1 hits,
+// top-k hits} and loss[1] (float64 sum) updated in fixed order
+void eval_metrics(const void* logits, const long long* labels, float* rowloss, int* rowrank, int B,
+                  int C, int k, long long* counts, double* loss, bool bf16, hipStream_t st);
 void spin_us(double us, hipStream_t st);
 // lenet_fused.hip: the whole LeNet training step in 2 dispatches
 int lenet_record_floats();

@@ -15,6 +15,7 @@ student for two strategies (sections/task3.tex:21-23):
 
 Both implement ``set_epoch`` (task3.tex:52) — the reference never calls it (B3);
 our training loops do.  ``MySampler`` is kept as the reference-named entry point.
+:class:`ShardSampler` is the evaluation counterpart: unpadded, unshuffled shards (B12).
 """
 from __future__ import annotations
 
@@ -119,6 +120,31 @@ class MySampler(_RankSampler):
 
     def indices(self):
         return self._impl.indices()
+
+
+class ShardSampler(Sampler):
+    """Evaluation shard: indices ``rank, rank + num_replicas, ...`` in dataset order.
+
+    Unlike the training samplers it does not pad to equal length (a padded test sample
+    would be counted twice) and does not shuffle: the shards are disjoint, cover the
+    dataset exactly, and differ in length by at most one."""
+
+    def __init__(self, dataset, num_replicas: int = 1, rank: int = 0):
+        if num_replicas < 1 or not (0 <= rank < num_replicas):
+            raise ValueError(f"invalid rank {rank} for num_replicas {num_replicas}")
+        self.dataset = dataset
+        self.n = len(dataset)
+        self.num_replicas = num_replicas
+        self.rank = rank
+
+    def __len__(self) -> int:
+        return len(range(self.rank, self.n, self.num_replicas))
+
+    def indices(self) -> torch.Tensor:
+        return torch.arange(self.rank, self.n, self.num_replicas)
+
+    def __iter__(self):
+        return iter(self.indices().tolist())
 
 
 def make_sampler(kind: str, dataset, num_replicas, rank, shuffle=True, seed=0):

@@ -275,3 +275,41 @@ def test(model, test_loader, print_fn=print):
     print_fn('\nTest set: Accuracy: {}/{} ({:.2f}%)\n'.format(c, size, 100 * c / size))
     model.train()
     return c / max(size, 1)
+
+
+@torch.no_grad()
+def evaluate(model, loader, k=5, sharded=False, print_fn=print):
+    """:func:`test` with top-k accuracy and the test loss (:class:`~dmlab.nn.loss.
+    EvalMetrics`: one kernel pair per batch, one host read at the end).  ``sharded``: every
+    rank calls this with a loader over its own :class:`~dmlab.data.ShardSampler` shard, the
+    metric state is summed over the process group and rank 0 prints.  The accuracy line is
+    the reference's (top-1); one more line carries top-k and the mean loss.  Returns
+    ``top1`` / ``topk`` (fractions), ``k``, ``test_loss`` and ``eval_samples``."""
+    from dmlab.nn.loss import EvalMetrics
+
+    model.eval()
+    device = getattr(loader, "device", None)
+    if device is None:
+        p = next(iter(model.parameters()), None)
+        device = p.device if p is not None else torch.device("cpu")
+    metrics = EvalMetrics(k, device=device)
+    talk = True
+    if sharded:
+        from dmlab.parallel import env
+
+        talk = env.get_rank() == 0
+    if talk:
+        print_fn("testing ...")
+    for inputs, labels in loader:
+        metrics.update(model(inputs), labels)
+    if sharded:
+        metrics.all_reduce()
+    r = metrics.result()
+    n, c = r["n"], r["top1"]
+    if talk:
+        print_fn('\nTest set: Accuracy: {}/{} ({:.2f}%)\n'.format(c, n, 100 * c / max(n, 1)))
+        print_fn('Test set: Top-{}: {}/{} ({:.2f}%), loss: {:.4f}'.format(
+            r["k"], r["topk"], n, 100 * r["topk"] / max(n, 1), r["loss"]))
+    model.train()
+    return {"top1": c / max(n, 1), "topk": r["topk"] / max(n, 1), "k": r["k"],
+            "test_loss": r["loss"], "eval_samples": n}

@@ -20,12 +20,12 @@ import json
 
 import torch
 
-from dmlab.data import DeviceLoader, MySampler, load_mnist
+from dmlab.data import DeviceLoader, MySampler, ShardSampler, load_mnist
 from dmlab.models import Net, ResNet18
 from dmlab.nn import CrossEntropyLoss
 from dmlab.optim import LARS, SGD, WarmupPolyLR
 from dmlab.parallel import DDP, comm, env
-from dmlab.tasks.common import test, train
+from dmlab.tasks.common import evaluate, test, train
 
 
 def dist_backend():
@@ -62,6 +62,15 @@ def parse_args(argv=None):
     p.add_argument("--warmup-steps", type=int, default=0,
                    help="> 0: linear warm-up over this many steps, then polynomial (power 2) "
                         "decay to 0 at the last step; 0 keeps --lr constant")
+    p.add_argument("--label-smoothing", type=float, default=0.0,
+                   help="train against (1-E)*onehot + E/C (the LARS ResNet recipes use 0.1); "
+                        "like --optimizer lars it needs the layer-wise loop")
+    p.add_argument("--topk", type=int, default=0,
+                   help="> 0: evaluation also reports top-K accuracy and the test loss; 0 "
+                        "keeps the reference's top-1 test")
+    p.add_argument("--eval", default="rank0", choices=["rank0", "sharded"],
+                   help="rank0: rank 0 evaluates the whole test set; sharded: every rank "
+                        "evaluates its unpadded shard and the metrics are all-reduced")
     p.add_argument("--bucket-mb", type=float, default=25.0)
     p.add_argument("--allreduce", default="auto", choices=["auto", "rccl", "xgmi"],
                    help="small-bucket all-reduce: RCCL ring or the one-shot xGMI kernel.  At "
@@ -98,7 +107,14 @@ def main(argv=None):
         raise SystemExit("--fused 1 runs constant-rate SGD inside the fused LeNet step; "
                          "--optimizer lars and --warmup-steps need the layer-wise loop "
                          "(--fused auto or 0)")
-    dev = env.init(a.n_devices, a.rank, a.master_addr, a.master_port, backend=a.backend,
+    if not 0.0 <= a.label_smoothing <= 1.0:
+        raise SystemExit("--label-smoothing must be in [0, 1]")
+    if a.fused == "1" and a.label_smoothing > 0:
+        raise SystemExit("--fused 1 computes its own unsmoothed loss inside the fused LeNet "
+                         "step; --label-smoothing needs the layer-wise loop (--fused auto or 0)")
+    if a.topk < 0:
+        raise SystemExit("--topk must be >= 0")
+    dev =env.init(a.n_devices, a.rank, a.master_addr, a.master_port, backend=a.backend,
                    device_type=a.device)
     rank, ws = env.get_rank(), env.get_world_size()
     checks = {}
@@ -166,7 +182,7 @@ def main(argv=None):
         agg = comm.GradAggregator(model, "allreduce", timing="events")
     fused = a.fused == "1" or (a.fused == "auto" and a.model == "lenet" and dev.type == "cuda"
                                and a.dp == "ddp" and a.optimizer == "sgd"
-                               and a.warmup_steps == 0)
+                               and a.warmup_steps == 0 and a.label_smoothing == 0)
     if fused:
         if a.model != "lenet" or dev.type != "cuda" or a.dp != "ddp":
             raise SystemExit("--fused 1 needs --model lenet on a GPU with --dp ddp")
@@ -188,10 +204,13 @@ def main(argv=None):
                 total = min(total, a.max_steps)
             sched = WarmupPolyLR(opt, min(a.warmup_steps, total), total)
             after_step = lambda _step: sched.step()  # noqa: E731
-        stats = train(net, loader, CrossEntropyLoss(), opt, a.epochs, rank=rank, aggregate=agg,
-                      batch_size=a.batch_size, max_steps=a.max_steps, after_step=after_step)
+        stats = train(net, loader, CrossEntropyLoss(a.label_smoothing), opt, a.epochs, rank=rank,
+                      aggregate=agg, batch_size=a.batch_size, max_steps=a.max_steps,
+                      after_step=after_step)
     if a.optimizer != "sgd":
         stats["optimizer"] = a.optimizer
+    if a.label_smoothing > 0:
+        stats["label_smoothing"] = a.label_smoothing
     print("Training time: {}".format(stats["train_time"]))
     if rank == 0:
         print("Throughput: {:.1f} samples/s (whole job, {} rank{})".format(
@@ -202,7 +221,14 @@ def main(argv=None):
         from dmlab.utils import checkpoint
 
         checkpoint.save(a.save, model, opt, epochs=a.epochs)
-    if not a.no_test and rank == 0:
+    sharded = a.eval == "sharded"
+    if not a.no_test and (sharded or (a.topk > 0 and rank == 0)):
+        # top-k and the test loss; sharded: every rank takes its unpadded shard of the test set
+        shard = ShardSampler(test_set, ws, rank) if sharded else None
+        ev = evaluate(model, DeviceLoader(test_set.to(dev, dtype=act), 32, sampler=shard),
+                      k=a.topk or 5, sharded=sharded)
+        stats.update(ev, accuracy=ev["top1"])
+    elif not a.no_test and a.topk == 0 and rank == 0:
         stats["accuracy"] = test(model, DeviceLoader(test_set.to(dev, dtype=act), 32))
     stats.update(checks)
     stats.update(rank=rank, world_size=ws, sampler=a.sampler, dp=a.dp,
