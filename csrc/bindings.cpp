@@ -439,6 +439,56 @@ void eval_metrics(at::Tensor logits, at::Tensor labels, at::Tensor rowloss, at::
 
 void spin_us(double us) { dm::spin_us(us, cur_stream()); }
 
+// (N,H,W,C) view of an image batch: a contiguous (N,H,W,C) tensor or a channels_last
+// (N,C,H,W) one, C = 1 or 3 -> sizes {N,H,W,C}
+std::array<int64_t, 4> aug_nhwc(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.dim() == 4, name, ": expected a 4-D image batch");
+  const auto c1 = t.size(1), c3 = t.size(3);
+  if ((c1 == 1 || c1 == 3) && t.permute({0, 2, 3, 1}).is_contiguous())
+    return {t.size(0), t.size(2), t.size(3), c1};
+  TORCH_CHECK((c3 == 1 || c3 == 3) && t.is_contiguous(), name,
+              ": expected (N,H,W,C) contiguous or (N,C,H,W) channels_last with C = 1 or 3");
+  return {t.size(0), t.size(1), t.size(2), c3};
+}
+
+// Gather + crop / resize / flip of a batch (csrc/augment.hip): out[b] = transform(params[b],
+// images[idx[b]]).  No allocation, no synchronisation.
+void augment_apply(at::Tensor images, at::Tensor idx, at::Tensor params, at::Tensor out) {
+  CHECK_CUDA(images); CHECK_CUDA(idx); CHECK_CUDA(params); CHECK_CUDA(out);
+  TORCH_CHECK(images.device() == idx.device() && images.device() == params.device() &&
+              images.device() == out.device(), "augment_apply: tensors on different devices");
+  const auto st = images.scalar_type();
+  TORCH_CHECK(st == at::kByte || st == at::kFloat || st == at::kBFloat16,
+              "images must be uint8, float32 or bfloat16");
+  TORCH_CHECK(out.scalar_type() == st, "out must have the dtype of images");
+  const auto is = aug_nhwc(images, "images");
+  const auto os = aug_nhwc(out, "out");
+  TORCH_CHECK(idx.scalar_type() == at::kLong && idx.dim() == 1 && idx.is_contiguous(),
+              "idx must be a contiguous int64 vector");
+  const int64_t B = idx.numel();
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.dim() == 2 && params.size(0) == B &&
+              params.size(1) == 8 && params.is_contiguous(), "params must be int32 [B,8]");
+  CHECK_ALIGN16(params);
+  TORCH_CHECK(os[0] == B && os[3] == is[3], "out must be (B,OH,OW,C) with the batch of idx and "
+              "the channels of images");
+  TORCH_CHECK(is[0] >= 1 && is[1] >= 1 && is[2] >= 1 && is[1] <= 16384 && is[2] <= 16384,
+              "images: empty or larger than 16384 x 16384");
+  TORCH_CHECK(os[1] >= 1 && os[2] >= 1 && os[1] <= 16384 && os[2] <= 16384,
+              "out: empty or larger than 16384 x 16384");
+  TORCH_CHECK(B < (1ll << 31) && B * os[1] * os[2] < (1ll << 38), "batch too large");
+  const char* ib = static_cast<const char*>(images.data_ptr());
+  const char* ob = static_cast<const char*>(out.data_ptr());
+  const int64_t esz = images.element_size();
+  const int64_t in_bytes = is[0] * is[1] * is[2] * is[3] * esz;
+  const int64_t out_bytes = B * os[1] * os[2] * os[3] * esz;
+  TORCH_CHECK(ob + out_bytes <= ib || ib + in_bytes <= ob, "out must not alias images");
+  if (B == 0) return;
+  const DeviceGuard guard(images.device());
+  dm::augment_apply(images.data_ptr(), (const long long*)idx.data_ptr(), params.data_ptr<int>(),
+                    out.data_ptr(), is[0], (int)is[1], (int)is[2], (int)is[3], (int)B, (int)os[1],
+                    (int)os[2], st == at::kByte ? 0 : st == at::kFloat ? 1 : 2, cur_stream());
+}
+
 // One LeNet training step (csrc/lenet_fused.hip).  w: conv1.w, conv1.b, conv2.w, conv2.b,
 // fc1.w, fc1.b, fc2.w, fc2.b (fp32 masters); off: flat-buffer offsets of fc2.w, fc2.b, fc1.w,
 // fc1.b, conv2.w, conv2.b, conv1.w, conv1.b; p/mom given: the SGD update runs in the same
@@ -578,6 +628,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cross_entropy_smooth", &cross_entropy_smooth);
   m.def("eval_metrics", &eval_metrics);
   m.def("spin_us", &spin_us);
+  m.def("augment_apply", &augment_apply);
   m.def("lenet_fused_step", &lenet_fused_step, "one fused LeNet training step (2 dispatches)",
         py::arg("x"), py::arg("labels"), py::arg("w"), py::arg("rec"), py::arg("cslab"),
         py::arg("rowloss"), py::arg("grad"), py::arg("off"), py::arg("p"), py::arg("mom"),

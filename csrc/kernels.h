@@ -68,6 +68,11 @@ void cross_entropy_smooth(const void* logits, const long long* labels, float* ro
 void eval_metrics(const void* logits, const long long* labels, float* rowloss, int* rowrank, int B,
                   int C, int k, long long* counts, double* loss, bool bf16, hipStream_t st);
 void spin_us(double us, hipStream_t st);
+// augment.hip: gather + crop / resize / flip of a batch in one launch.  images (N,H,W,C), C = 1
+// or 3; params int32 [B,8] (16-B aligned); out (B,OH,OW,C); dtype 0 = u8, 1 = fp32, 2 = bf16
+void augment_apply(const void* images, const long long* idx, const int* params, void* out,
+                   long long N, int H, int W, int C, int B, int OH, int OW, int dtype,
+                   hipStream_t st);
 // lenet_fused.hip: the whole LeNet training step in 2 dispatches
 int lenet_record_floats();
 int lenet_slab_floats();

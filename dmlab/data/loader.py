@@ -5,13 +5,17 @@ tensor per sample, ``num_workers=0``) and copies every batch with ``.cuda()``
 (task1/pytorch/model.py:47, task2/model.py:52).  Here the whole
 dataset lives on the device (MNIST is 188 MB fp32 — nothing against 288 GB of
 HBM3E) and a batch is one ``index_select`` gather driven by the sampler's index
-list, which is itself uploaded once per epoch.
+list, which is itself uploaded once per epoch.  With a ``transform``
+(:class:`~dmlab.data.augment.DeviceAugment`) the gather happens inside the augmentation
+kernel instead, driven by the same index list plus a per-sample parameter table.
 """
 from __future__ import annotations
 
 from typing import NamedTuple
 
 import torch
+
+from .augment import image_size
 
 
 class Gathered(NamedTuple):
@@ -72,8 +76,9 @@ class DeviceCursor:
 
 class DeviceLoader:
     def __init__(self, dataset, batch_size: int, sampler=None, shuffle: bool = False,
-                 drop_last: bool = False, seed: int = 0, device=None):
+                 drop_last: bool = False, seed: int = 0, device=None, transform=None):
         self.dataset = dataset
+        self.transform = transform
         self.batch_size = int(batch_size)
         self.sampler = sampler
         self.shuffle = shuffle
@@ -111,7 +116,32 @@ class DeviceLoader:
         n = len(self.sampler) if self.sampler is not None else len(self.dataset)
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
+    def _device_indices_params(self):
+        """The epoch's index list and the transform's parameter table for exactly those
+        indices (computed on the host once per epoch), uploaded the same way."""
+        idx = self._indices()
+        par = self.transform.params(idx, self.epoch, size=image_size(self.dataset.images))
+        if self.device.type == "cuda":
+            return (idx.pin_memory().to(self.device, non_blocking=True),
+                    par.pin_memory().to(self.device, non_blocking=True))
+        return idx.to(self.device), par.to(self.device)
+
+    def _iter_transformed(self):
+        """(augmented images, labels) batches: the transform gathers the rows itself, and
+        every batch is a fresh tensor (a consumer may keep it until its backward pass)."""
+        idx, par = self._device_indices_params()
+        n = idx.numel()
+        bs = self.batch_size
+        stop = (n // bs) * bs if self.drop_last else n
+        im, lb = self.dataset.images, self.dataset.labels
+        for s in range(0, stop, bs):
+            sl = idx[s: s + bs]
+            yield self.transform.apply(im, sl, par[s: s + bs]), lb.index_select(0, sl)
+
     def __iter__(self):
+        if self.transform is not None:
+            yield from self._iter_transformed()
+            return
         idx = self._device_indices()
         n = idx.numel()
         bs = self.batch_size
@@ -122,7 +152,11 @@ class DeviceLoader:
     def iter_gathered(self):
         """Like iteration, but yields ``(Gathered(images, idx), labels)``: the image gather is
         left to the consumer (fused into the ResNet stem's input packing); labels are
-        gathered (B int64)."""
+        gathered (B int64).  With a transform the batch is the augmented tensor itself, as
+        in plain iteration: the gather already happened inside the augmentation kernel."""
+        if self.transform is not None:
+            yield from self._iter_transformed()
+            return
         idx = self._device_indices()
         n = idx.numel()
         bs = self.batch_size
@@ -134,4 +168,8 @@ class DeviceLoader:
 
     def cursor(self) -> DeviceCursor:
         """Device-resident epoch order + cursor, for hipGraph-captured steps."""
+        if self.transform is not None:
+            raise ValueError("DeviceLoader.cursor() is not available with a transform: the "
+                             "fused LeNet step reads the dataset rows itself and would skip "
+                             "the augmentation; iterate the loader instead")
         return DeviceCursor(self)

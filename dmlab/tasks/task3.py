@@ -20,7 +20,7 @@ import json
 
 import torch
 
-from dmlab.data import DeviceLoader, MySampler, ShardSampler, load_mnist
+from dmlab.data import DeviceAugment, DeviceLoader, MySampler, ShardSampler, load_mnist
 from dmlab.models import Net, ResNet18
 from dmlab.nn import CrossEntropyLoss
 from dmlab.optim import LARS, SGD, WarmupPolyLR
@@ -71,6 +71,17 @@ def parse_args(argv=None):
     p.add_argument("--eval", default="rank0", choices=["rank0", "sharded"],
                    help="rank0: rank 0 evaluates the whole test set; sharded: every rank "
                         "evaluates its unpadded shard and the metrics are all-reduced")
+    p.add_argument("--augment", default="none", choices=["none", "pad-crop", "rrc"],
+                   help="on-device training augmentation, drawn per (seed, dataset index, "
+                        "epoch): pad-crop = zero-pad by --aug-pad and crop at a random offset; "
+                        "rrc = random resized crop to the image size (evaluation then uses "
+                        "the centre crop).  Like --optimizer lars it needs the layer-wise loop")
+    p.add_argument("--aug-pad", type=int, default=4, help="pad-crop: padding in pixels")
+    p.add_argument("--aug-scale", type=float, nargs=2, default=(0.08, 1.0), metavar=("LO", "HI"),
+                   help="rrc: range of the crop's area as a fraction of the image")
+    p.add_argument("--aug-flip", type=float, default=None,
+                   help="horizontal-flip probability (default 0.5 for resnet18, 0 for lenet)")
+    p.add_argument("--aug-seed", type=int, default=0)
     p.add_argument("--bucket-mb", type=float, default=25.0)
     p.add_argument("--allreduce", default="auto", choices=["auto", "rccl", "xgmi"],
                    help="small-bucket all-reduce: RCCL ring or the one-shot xGMI kernel.  At "
@@ -114,6 +125,22 @@ def main(argv=None):
                          "step; --label-smoothing needs the layer-wise loop (--fused auto or 0)")
     if a.topk < 0:
         raise SystemExit("--topk must be >= 0")
+    if a.fused == "1" and a.augment != "none":
+        raise SystemExit("--fused 1 reads the dataset rows inside the fused LeNet step; "
+                         "--augment needs the layer-wise loop (--fused auto or 0)")
+    aug = None
+    if a.augment != "none":
+        if a.aug_flip is None:
+            a.aug_flip = 0.5 if a.model == "resnet18" else 0.0
+        try:
+            side = a.image_size if a.model == "resnet18" else 28
+            if a.augment == "pad-crop":
+                aug = DeviceAugment.pad_crop(a.aug_pad, flip=a.aug_flip, seed=a.aug_seed)
+            else:
+                aug = DeviceAugment.random_resized_crop(side, scale=tuple(a.aug_scale),
+                                                        flip=a.aug_flip, seed=a.aug_seed)
+        except ValueError as e:
+            raise SystemExit(f"--augment: {e}")
     dev =env.init(a.n_devices, a.rank, a.master_addr, a.master_port, backend=a.backend,
                    device_type=a.device)
     rank, ws = env.get_rank(), env.get_world_size()
@@ -160,7 +187,11 @@ def main(argv=None):
     # keeps fp32)
     act = torch.bfloat16 if (a.dtype == "bf16" and a.model == "lenet" and dev.type == "cuda") \
         else None
-    loader = DeviceLoader(train_set.to(dev, dtype=act), a.batch_size, sampler=sampler)
+    if aug is None:
+        loader = DeviceLoader(train_set.to(dev, dtype=act), a.batch_size, sampler=sampler)
+    else:  # the augmentation kernel reads channel-innermost rows
+        loader = DeviceLoader(train_set.to(dev, dtype=act, memory_format=torch.channels_last),
+                              a.batch_size, sampler=sampler, transform=aug)
     if a.optimizer == "lars":
         opt = LARS(model.parameters(), lr=a.lr, momentum=a.momentum,
                    weight_decay=a.weight_decay, trust_coefficient=a.trust_coef)
@@ -182,7 +213,8 @@ def main(argv=None):
         agg = comm.GradAggregator(model, "allreduce", timing="events")
     fused = a.fused == "1" or (a.fused == "auto" and a.model == "lenet" and dev.type == "cuda"
                                and a.dp == "ddp" and a.optimizer == "sgd"
-                               and a.warmup_steps == 0 and a.label_smoothing == 0)
+                               and a.warmup_steps == 0 and a.label_smoothing == 0
+                               and aug is None)
     if fused:
         if a.model != "lenet" or dev.type != "cuda" or a.dp != "ddp":
             raise SystemExit("--fused 1 needs --model lenet on a GPU with --dp ddp")
@@ -211,6 +243,8 @@ def main(argv=None):
         stats["optimizer"] = a.optimizer
     if a.label_smoothing > 0:
         stats["label_smoothing"] = a.label_smoothing
+    if aug is not None:
+        stats.update(augment=a.augment, aug_seed=a.aug_seed, aug_flip=a.aug_flip)
     print("Training time: {}".format(stats["train_time"]))
     if rank == 0:
         print("Throughput: {:.1f} samples/s (whole job, {} rank{})".format(
@@ -222,14 +256,18 @@ def main(argv=None):
 
         checkpoint.save(a.save, model, opt, epochs=a.epochs)
     sharded = a.eval == "sharded"
+    ev_kw = {}
+    if a.augment == "rrc":  # evaluate on the deterministic centre crop of the same size
+        ev_kw = dict(transform=aug.eval())
+        test_set = test_set.to(dev, dtype=act, memory_format=torch.channels_last)
     if not a.no_test and (sharded or (a.topk > 0 and rank == 0)):
         # top-k and the test loss; sharded: every rank takes its unpadded shard of the test set
         shard = ShardSampler(test_set, ws, rank) if sharded else None
-        ev = evaluate(model, DeviceLoader(test_set.to(dev, dtype=act), 32, sampler=shard),
+        ev = evaluate(model, DeviceLoader(test_set.to(dev, dtype=act), 32, sampler=shard, **ev_kw),
                       k=a.topk or 5, sharded=sharded)
         stats.update(ev, accuracy=ev["top1"])
     elif not a.no_test and a.topk == 0 and rank == 0:
-        stats["accuracy"] = test(model, DeviceLoader(test_set.to(dev, dtype=act), 32))
+        stats["accuracy"] = test(model, DeviceLoader(test_set.to(dev, dtype=act), 32, **ev_kw))
     stats.update(checks)
     stats.update(rank=rank, world_size=ws, sampler=a.sampler, dp=a.dp,
                  samples_per_s=stats["samples"] * ws / stats["train_time"])
