@@ -65,34 +65,15 @@ const unsigned char* bit_mask(const c10::optional<at::Tensor>& m, const at::Tens
   return m->data_ptr<uint8_t>();
 }
 
-// The folded BatchNorm-backward operand (kernels.h BnBwdIn) of a weight gradient whose dY
-// argument is that BN's OUTPUT gradient dz: y (its input, dz's shape), coef [3][C] (a, b, c of
-// dy = a*dz' + b*y + c), scale/shift (ReLU mask from y) or the 1-bit mask, neither: no ReLU
-dm::BnBwdIn bwd_in(const at::Tensor& dz, const at::Tensor& y, const at::Tensor& coef,
-                   const c10::optional<at::Tensor>& sc, const c10::optional<at::Tensor>& sh,
-                   const c10::optional<at::Tensor>& mask) {
-  need_bf16_nhwc(y, "bwd_y");
-  TORCH_CHECK(y.sizes() == dz.sizes(), "bwd_y: the gradient's shape");
-  const int C = dz.size(3);
-  need_f32(coef, "bwd_coef", 3 * C);
-  // unused scale/shift alias coef: the kernels load them unconditionally (kernels.h BnBwdIn)
-  dm::BnBwdIn b{bp(y), nullptr, fp(coef), fp(coef), fp(coef), C, 0};
-  TORCH_CHECK(!(mask.has_value() && sc.has_value()), "bwd: mask or scale/shift, not both");
-  if (sc.has_value()) {
-    TORCH_CHECK(sh.has_value(), "bwd_scale needs bwd_shift");
-    need_f32(*sc, "bwd_scale", C);
-    need_f32(*sh, "bwd_shift", C);
-    b.sc = fp(*sc);
-    b.sh = fp(*sh);
-    b.mode = 2;
-  }
-  if (mask.has_value()) {
-    TORCH_CHECK(mask->is_cuda() && mask->scalar_type() == at::kByte && mask->is_contiguous() &&
-                    mask->numel() * 8 == dz.numel(), "bwd_mask: uint8 [numel/8]");
-    b.mask = mask->data_ptr<uint8_t>();
-    b.mode = 4;
-  }
-  return b;
+// The fused pre-BN operand of a conv over `x` (the kernel stages relu(x*scale + shift)):
+// the checked {scale, shift} pointers
+std::pair<const float*, const float*> pre_bn(const c10::optional<at::Tensor>& scale,
+                                             const c10::optional<at::Tensor>& shift,
+                                             const at::Tensor& x) {
+  TORCH_CHECK(shift.has_value(), "pre_scale needs pre_shift");
+  need_f32(*scale, "pre_scale", x.size(3));
+  need_f32(*shift, "pre_shift", x.size(3));
+  return {fp(*scale), fp(*shift)};
 }
 
 // y = conv(x, w)  (+add) ; stats [T][2][Cout] optional
@@ -122,11 +103,9 @@ void conv_fwd(at::Tensor x, at::Tensor wpack, at::Tensor y, c10::optional<at::Te
   const DeviceGuard guard(x.device());
   if (pre_scale.has_value()) {
     int bn, waves;
-    TORCH_CHECK(pre_shift.has_value(), "pre_scale needs pre_shift");
-    need_f32(*pre_scale, "pre_scale", x.size(3));
-    need_f32(*pre_shift, "pre_shift", x.size(3));
+    const auto [psc, psh] = pre_bn(pre_scale, pre_shift, x);
     if (cfg == 80) {
-      dm::conv_res64(bp(x), bp(wpack), bp(y), ap, sp, g, cur_stream(), fp(*pre_scale), fp(*pre_shift));
+      dm::conv_res64(bp(x), bp(wpack), bp(y), ap, sp, g, cur_stream(), psc, psh);
       return;
     }
     // the pipelined tiles take no fused pre-BN (measured slower than materialising it): the
@@ -134,8 +113,7 @@ void conv_fwd(at::Tensor x, at::Tensor wpack, at::Tensor y, c10::optional<at::Te
     if (cfg >= 90 && cfg <= 93) cfg = 41;
     TORCH_CHECK(dm::halo_cfg((int)cfg, bn, waves) && dm::conv_halo_supported(g),
                 "fused pre-BN needs a halo-kernel cfg and a unit-stride 3x3 geometry");
-    dm::conv_halo(bp(x), bp(wpack), bp(y), ap, sp, g, bn, waves, cur_stream(), fp(*pre_scale),
-                  fp(*pre_shift));
+    dm::conv_halo(bp(x), bp(wpack), bp(y), ap, sp, g, bn, waves, cur_stream(), psc, psh);
     return;
   }
   dm::igemm_fwd(bp(x), bp(wpack), bp(y), ap, sp, g, cfg, cur_stream());
@@ -343,13 +321,9 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
 void conv_wgrad(at::Tensor x, at::Tensor dy, at::Tensor dw, at::Tensor slab, int64_t Cin,
                 int64_t KH, int64_t KW, int64_t stride, int64_t pad, double beta, int64_t S,
                 int64_t cfg, bool s2d, c10::optional<at::Tensor> pre_scale,
-                c10::optional<at::Tensor> pre_shift, c10::optional<at::Tensor> bwd_y,
-                c10::optional<at::Tensor> bwd_coef, c10::optional<at::Tensor> bwd_scale,
-                c10::optional<at::Tensor> bwd_shift, c10::optional<at::Tensor> bwd_mask) {
+                c10::optional<at::Tensor> pre_shift) {
   // s2d: x/dy are the space-to-depth stem operands (4x4/s1 conv over 4*Cin channels);
   // dw is the original [Cout][Cin][7][7] gradient
-  // bwd_* (optional, cfg 4): dy is a BatchNorm's OUTPUT gradient; the halo weight gradient
-  // stages that BN's backward a*dz' + b*y + c itself (bwd_in)
   need_bf16_nhwc(x, "x");
   need_bf16_nhwc(dy, "dy");
   const int Cout = dy.size(3);
@@ -361,25 +335,10 @@ void conv_wgrad(at::Tensor x, at::Tensor dy, at::Tensor dw, at::Tensor slab, int
   const long long mchunk = ((steps + S - 1) / S) * 64;  // multiple of both kernels' row step
   const DeviceGuard guard(x.device());
   auto st = cur_stream();
-  if (bwd_y.has_value()) {
-    TORCH_CHECK(cfg == 4 && !s2d && bwd_coef.has_value() && dm::wgrad_halo_supported(g),
-                "bwd_*: the 9-tap halo weight gradient (cfg 4), a 3x3/s1/p1 geometry, bwd_coef");
-    const dm::BnBwdIn bwd = bwd_in(dy, *bwd_y, *bwd_coef, bwd_scale, bwd_shift, bwd_mask);
-    const float *psc = nullptr, *psh = nullptr;
-    if (pre_scale.has_value()) {
-      TORCH_CHECK(pre_shift.has_value(), "pre_scale needs pre_shift");
-      need_f32(*pre_scale, "pre_scale", x.size(3));
-      need_f32(*pre_shift, "pre_shift", x.size(3));
-      psc = fp(*pre_scale);
-      psh = fp(*pre_shift);
-    }
-    dm::wgrad_halo(bp(x), bp(dy), fp(slab), g, (int)S, mchunk, 3, st, psc, psh, &bwd);
-  } else if (pre_scale.has_value()) {
+  if (pre_scale.has_value()) {
     // x = previous conv's raw output, operand relu(x*sc + sh)
     TORCH_CHECK(pre_shift.has_value() && !s2d, "pre_scale needs pre_shift (not with s2d)");
-    need_f32(*pre_scale, "pre_scale", x.size(3));
-    need_f32(*pre_shift, "pre_shift", x.size(3));
-    const float *psc = fp(*pre_scale), *psh = fp(*pre_shift);
+    const auto [psc, psh] = pre_bn(pre_scale, pre_shift, x);
     if (cfg == 8) {
       dm::wgrad_res64(bp(x), bp(dy), fp(slab), g, (int)S, st, psc, psh);
     } else {
@@ -880,10 +839,7 @@ void register_resnet(pybind11::module_& m) {
   m.def("conv_wgrad", &conv_wgrad, py::arg("x"), py::arg("dy"), py::arg("dw"), py::arg("slab"),
         py::arg("Cin"), py::arg("KH"), py::arg("KW"), py::arg("stride"), py::arg("pad"),
         py::arg("beta"), py::arg("S"), py::arg("cfg"), py::arg("s2d"),
-        py::arg("pre_scale") = py::none(), py::arg("pre_shift") = py::none(),
-        py::arg("bwd_y") = py::none(), py::arg("bwd_coef") = py::none(),
-        py::arg("bwd_scale") = py::none(), py::arg("bwd_shift") = py::none(),
-        py::arg("bwd_mask") = py::none());
+        py::arg("pre_scale") = py::none(), py::arg("pre_shift") = py::none());
   m.def("pack_weights", &pack_weights);
   m.def("pack_weights_tiled", &pack_weights_tiled);
   m.def("bn_stats_finalize", &bn_stats_finalize, py::arg("stats"), py::arg("T"), py::arg("count"),

@@ -159,24 +159,6 @@ struct BnBwdRed {
   const float* is;
   float* part;
 };
-// The BatchNorm backward apply folded into the 9-tap halo weight gradient's dY staging (the conv
-// that produced that BN's input): the staged operand is the BN's OUTPUT gradient dz, and the
-// kernel stages dy = a*dz' + b*y + c (dz' = dz where the ReLU passed: y*sc + sh > 0 when sc is
-// set, bit j of the 1-bit mask when mask is set, everywhere when neither) instead of reading a
-// materialised dy.  coef: [3][C] a, b, c.  No model path uses it (measured slower,
-// docs/KERNELS.md).
-// Every pointer is valid (sc / sh alias coef when unused) and `mode` says which mask applies
-// (0: none, 2: y*sc + sh > 0, 4: the 1-bit mask), so the kernel loads unconditionally: a load
-// under a branch leaves a phi that makes the compiler drain every prefetch in flight.
-struct BnBwdIn {
-  const bf16_t* y;
-  const uint8_t* mask;  // null unless mode 4 (read through a range-checked buffer resource)
-  const float* coef;
-  const float* sc;
-  const float* sh;
-  int C;
-  int mode;
-};
 // conv_pipe.hip: pipelined LDS-DMA implicit-GEMM conv (cfg 90-93: 256-pixel tiles)
 bool conv_pipe_supported(const ConvGeom& g, int cfg);
 bool conv_pipe_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
@@ -209,7 +191,7 @@ void wgrad_res64(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom&
                  hipStream_t st, const float* pre_sc = nullptr, const float* pre_sh = nullptr);
 void wgrad_halo(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
                 long long mchunk, int nty, hipStream_t st, const float* pre_sc = nullptr,
-                const float* pre_sh = nullptr, const BnBwdIn* bwd = nullptr);
+                const float* pre_sh = nullptr);
 void pack_weights_tiled(const long long* desc, const int* tprefix, int nl, int ntiles,
                         hipStream_t st);
 int igemm_fwd_rowtile(int cfg);

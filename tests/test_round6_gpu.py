@@ -211,67 +211,11 @@ def test_resnet18_step_merged_shortcut(dev, merge, monkeypatch):
         assert not merged and s2, calls
 
 
-# ------------------------------------------------------------------ BN-backward apply folded
-# into the 9-tap halo weight gradient (cfg 4): a kernel path no model step takes
-FOLD_GEOMS = [(2, 28, 128, 128), (3, 14, 128, 128), (2, 8, 64, 128), (4, 7, 128, 64)]
-
-
-def _fold_operands(dev, N, H, Cin, Cout, mode, seed):
-    """dz (the BN's output gradient), y (its input), coef [3][Cout], scale/shift, mask, and the
-    dy = a*dz' + b*y + c the kernels must stage, in float64 from the bf16 operands."""
-    g = torch.Generator(device=dev).manual_seed(seed)
-    dz = torch.randn(N, H, H, Cout, device=dev, generator=g).bfloat16()
-    y = (torch.randn(N, H, H, Cout, device=dev, generator=g) * 1.5 + 0.2).bfloat16()
-    coef = torch.randn(3, Cout, device=dev, generator=g) * torch.tensor([[1.0], [0.3], [0.1]], device=dev)
-    sc = torch.rand(Cout, device=dev, generator=g) + 0.5
-    sh = torch.randn(Cout, device=dev, generator=g) * 0.5
-    keep = torch.rand(N, H, H, Cout, device=dev, generator=g) > 0.45
-    kw = dict(bwd_y=y, bwd_coef=coef.reshape(-1).contiguous())
-    if mode == 2:
-        kw.update(bwd_scale=sc, bwd_shift=sh)
-        pas = y.float() * sc + sh > 0
-    elif mode == 4:
-        kw["bwd_mask"] = _bits(keep)
-        pas = keep
-    else:
-        pas = torch.ones_like(keep)
-    d = torch.where(pas, dz.float(), torch.zeros((), device=dev))
-    dy = coef[0] * d + coef[1] * y.float() + coef[2]
-    return g, dz, y, kw, dy
-
-
-@pytest.mark.parametrize("geom", FOLD_GEOMS)
-@pytest.mark.parametrize("mode", [0, 2, 4])
-@pytest.mark.parametrize("pre", [False, True])
-def test_folded_bn_backward_wgrad(dev, geom, mode, pre):
-    """9-tap halo weight gradient staging a*dz' + b*y + c (with and without the fused pre-BN
-    of its input) vs float64 conv2d_weight of the materialised dy."""
-    N, H, Cin, Cout = geom
-    g, dz, y, kw, dyf = _fold_operands(dev, N, H, Cin, Cout, mode, 55)
-    x = torch.randn(N, H, H, Cin, device=dev, generator=g).bfloat16()
-    pk = {}
-    xr = x.double()
-    if pre:
-        psc = torch.rand(Cin, device=dev, generator=g) + 0.5
-        psh = torch.randn(Cin, device=dev, generator=g) * 0.5
-        pk = dict(pre_scale=psc, pre_shift=psh)
-        xr = torch.relu(x.float() * psc + psh).bfloat16().double()
-    S = 4
-    slab = torch.empty(S * Cout * 9 * Cin, device=dev)
-    dw = torch.empty(Cout, Cin, 3, 3, device=dev)
-    lib().conv_wgrad(x, dz, dw, slab, Cin, 3, 3, 1, 1, 0.0, S, 4, False, **pk, **kw)
-    ref = torch.nn.grad.conv2d_weight(_nchw(xr), (Cout, Cin, 3, 3), _nchw(dyf.bfloat16()).double(), 1, 1)
-    err = ((dw.double() - ref).norm() / ref.norm()).item()
-    assert err < 2e-3, err
-
-
-@pytest.mark.parametrize("fold", ["0"])
-def test_resnet18_step_bn_fold(dev, fold, monkeypatch):
+def test_resnet18_step_layer2_halo_kernels(dev, monkeypatch):
     """Whole native ResNet-18 step at 8 x 3 x 112 x 112: held to the bf16-autocast error envelope
     of the fp32 step per parameter; layer 2 (128 channels at 14 x 14) really runs the halo
     kernels, its stride-1 data gradients on cfg 42 and their weight gradients on the 9-tap tile
-    (wgrad cfg 4), and no launch takes a folded BN-backward operand (conv_wgrad's bwd_*)
-    now that the switch which selected it (the "1" case) is gone."""
+    (wgrad cfg 4)."""
     import copy
 
     import torch.nn.functional as F
@@ -291,7 +235,7 @@ def test_resnet18_step_bn_fold(dev, fold, monkeypatch):
 
             def wrapped(*a, **k):
                 i = 8 if n == "conv_dgrad" else 11  # cfg's position in each signature
-                calls.append((n, a[i] if len(a) > i else k.get("cfg"), "bwd_y" in k))
+                calls.append((n, a[i] if len(a) > i else k.get("cfg")))
                 return f(*a, **k)
             return wrapped
 
@@ -320,5 +264,19 @@ def test_resnet18_step_bn_fold(dev, fold, monkeypatch):
         if rn > 1.5 * rc + 0.05:
             bad.append((n, rn, rc))
     assert not bad, bad
-    assert ("conv_dgrad", 42, False) in calls and ("conv_wgrad", 4, False) in calls, calls
-    assert not [c_ for c_ in calls if c_[2]], calls
+    assert ("conv_dgrad", 42) in calls and ("conv_wgrad", 4) in calls, calls
+
+
+def test_conv_wgrad_refuses_folded_bn_backward(dev):
+    """The BN-backward fold is gone from the halo weight gradient: conv_wgrad no longer takes a
+    bwd_* operand, so the call is rejected as an unknown keyword before any launch."""
+    N, H, C = 1, 8, 64
+    x = torch.zeros(N, H, H, C, device=dev, dtype=torch.bfloat16)
+    dz, y = torch.zeros_like(x), torch.zeros_like(x)
+    coef = torch.zeros(3 * C, device=dev)
+    S = 1
+    slab = torch.empty(S * C * 9 * C, device=dev)
+    dw = torch.empty(C, C, 3, 3, device=dev)
+    with pytest.raises(TypeError):
+        lib().conv_wgrad(x, dz, dw, slab, C, 3, 3, 1, 1, 0.0, S, 4, False, bwd_y=y, bwd_coef=coef)
+    lib().conv_wgrad(x, dz, dw, slab, C, 3, 3, 1, 1, 0.0, S, 4, False)  # the same call without it
