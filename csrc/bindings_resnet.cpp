@@ -5,6 +5,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include "conv_cfg.h"
 #include "conv_geom.h"
 #include "kernels.h"
 
@@ -54,7 +55,19 @@ dm::ConvGeom fwd_geom(const at::Tensor& x, int Cout, int KH, int KW, int stride,
   return g;
 }
 
-int64_t conv_stats_rows(int64_t M, int64_t cfg, int64_t ncols);
+// the rows of csrc/conv_cfg.h behind a cfg argument
+const dm::ConvCfg& cfg_of(int64_t cfg) {
+  const dm::ConvCfg* c = dm::conv_cfg((int)cfg);
+  TORCH_CHECK(c, "unknown cfg ", cfg);
+  return *c;
+}
+
+// statistics rows a forward conv of this cfg writes (one per row tile, or per workgroup of the
+// persistent res64 kernel)
+int64_t conv_stats_rows(int64_t M, int64_t cfg) {
+  const int bm = cfg_of(cfg).rowtile;
+  return bm ? (M + bm - 1) / bm : dm::res64_grid(M);
+}
 
 // A 1-bit mask over the elements of `of` (bit j of byte i = element 8i + j), or null
 const unsigned char* bit_mask(const c10::optional<at::Tensor>& m, const at::Tensor& of,
@@ -93,51 +106,107 @@ void conv_fwd(at::Tensor x, at::Tensor wpack, at::Tensor y, c10::optional<at::Te
   TORCH_CHECK(wpack.scalar_type() == at::kBFloat16 && wpack.numel() == (int64_t)Cout * KH * KW * x.size(3),
               "wpack must be bf16 [Cout][KH][KW][C]");
   auto g = fwd_geom(x, Cout, KH, KW, stride, pad, OH, OW);
+  const dm::ConvCfg* c = &cfg_of(cfg);
   float* sp = nullptr;
   if (stats.has_value()) {
-    need_f32(*stats, "stats", conv_stats_rows(g.M, cfg, Cout) * 2 * Cout);
+    need_f32(*stats, "stats", conv_stats_rows(g.M, cfg) * 2 * Cout);
     sp = fp(*stats);
   }
   const bf* ap = nullptr;
   if (add.has_value()) { need_bf16_nhwc(*add, "add"); TORCH_CHECK(add->sizes() == y.sizes()); ap = bp(*add); }
   const DeviceGuard guard(x.device());
   if (pre_scale.has_value()) {
-    int bn, waves;
     const auto [psc, psh] = pre_bn(pre_scale, pre_shift, x);
-    if (cfg == 80) {
+    // a tile that takes no fused pre-BN may name the one (same statistics slab rows) that does
+    if (c->pre_reroute) c = &cfg_of(c->pre_reroute);
+    if (c->pre_bn && c->family == dm::ConvFamily::res64) {
       dm::conv_res64(bp(x), bp(wpack), bp(y), ap, sp, g, cur_stream(), psc, psh);
       return;
     }
-    // the pipelined tiles take no fused pre-BN (measured slower than materialising it): the
-    // halo tile with the same 256-row stats slab does
-    if (cfg >= 90 && cfg <= 93) cfg = 41;
-    TORCH_CHECK(dm::halo_cfg((int)cfg, bn, waves) && dm::conv_halo_supported(g),
+    TORCH_CHECK(c->pre_bn && c->family == dm::ConvFamily::halo && dm::conv_halo_supported(g),
                 "fused pre-BN needs a halo-kernel cfg and a unit-stride 3x3 geometry");
-    dm::conv_halo(bp(x), bp(wpack), bp(y), ap, sp, g, bn, waves, cur_stream(), psc, psh);
+    dm::conv_halo(bp(x), bp(wpack), bp(y), ap, sp, g, c->bn, c->halo_waves, cur_stream(), psc, psh);
     return;
   }
   dm::igemm_fwd(bp(x), bp(wpack), bp(y), ap, sp, g, cfg, cur_stream());
 }
 
-// part rows of a stride-2 data gradient with the reduction epilogue (conv_dgrad red_part)
-int64_t dgrad_s2_red_rows(int64_t N, int64_t H, int64_t W, int64_t cfg) {
-  dm::ConvGeomSet set{};
-  int ng = 0;
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) {
-      auto& g = set.g[ng++];
-      g.M = N * ((H - a + 1) / 2) * ((W - b + 1) / 2);
-    }
-  if (cfg >= 90 && cfg <= 93) return dm::pipe_multi_rows(set, ng);
-  return dm::igemm_multi_rows(set, ng, (int)cfg);
+// A data gradient as a forward-style GEMM: dy [N,OH,OW,Cout] is the input, dx [N,H,W,Cin] the
+// output, wd the packed weights; the tap grid is filled in per stride below
+dm::ConvGeom dgrad_base(int N, int OH, int OW, int Cout, int H, int W, int Cin, int KH, int KW) {
+  dm::ConvGeom g{};
+  g.N = N; g.H = OH; g.W = OW; g.C = Cout; g.lgC8 = ilog2(Cout / 8);
+  g.OH = H; g.OW = W; g.OC = Cin;
+  g.KW = KW; g.Ncols = Cin; g.wK = KH * KW * Cout;
+  return g;
 }
 
-// statistics rows a forward conv of this cfg writes (one per row tile, or per workgroup of the
-// persistent cfg 80); ncols is unused
-int64_t conv_stats_rows(int64_t M, int64_t cfg, int64_t ncols) {
-  if (cfg == 80) return dm::res64_grid(M);
-  const int bm = dm::igemm_fwd_rowtile(cfg);
-  return (M + bm - 1) / bm;
+dm::ConvGeom dgrad_s1_geom(const dm::ConvGeom& base, int KH, int KW, int pad) {
+  auto g = base;
+  g.Hg = g.OH; g.Wg = g.OW; g.isy = 1; g.isx = 1; g.osy = 1; g.osx = 1; g.oy0 = 0; g.ox0 = 0;
+  g.nth = KH; g.ntw = KW; g.dy0 = pad; g.dys = -1; g.dx0 = pad; g.dxs = -1;
+  g.kh0 = 0; g.khs = 1; g.kw0 = 0; g.kws = 1;
+  g.M = (long long)g.N * g.OH * g.OW; g.K = KH * KW * g.C;
+  dm::geom_finalize(g);
+  return g;
+}
+
+// The parity classes of a stride-2 data gradient: class (a, b) writes the output pixels
+// (2y + a, 2x + b), which are disjoint.  The classes go into set a-major and their count is
+// returned; one without pixels or without taps is left out (any_empty: some class has no taps,
+// e.g. the odd pixels of a 1x1/s2 conv, so its pixels are exactly zero)
+int dgrad_s2_classes(const dm::ConvGeom& base, int KH, int KW, int pad, dm::ConvGeomSet& set,
+                     bool& any_empty) {
+  int ng = 0;
+  any_empty = false;
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b) {
+      auto g = base;
+      const int kh0 = (a + pad) & 1, kw0 = (b + pad) & 1;
+      const int nth = (KH - kh0 + 1) / 2, ntw = (KW - kw0 + 1) / 2;
+      if (nth <= 0 || ntw <= 0) { any_empty = true; continue; }
+      g.Hg = (g.OH - a + 1) / 2; g.Wg = (g.OW - b + 1) / 2;
+      if (g.Hg <= 0 || g.Wg <= 0) continue;
+      g.isy = 1; g.isx = 1; g.osy = 2; g.osx = 2; g.oy0 = a; g.ox0 = b;
+      g.nth = nth; g.ntw = ntw;
+      g.dy0 = (a + pad - kh0) / 2; g.dys = -1; g.dx0 = (b + pad - kw0) / 2; g.dxs = -1;
+      g.kh0 = kh0; g.khs = 2; g.kw0 = kw0; g.kws = 2;
+      g.M = (long long)g.N * g.Hg * g.Wg; g.K = nth * ntw * g.C;
+      dm::geom_finalize(g);
+      set.g[ng++] = g;
+    }
+  return ng;
+}
+
+// part rows of the classes' single launch with the reduction epilogue (class major, row tile
+// minor; every block writes its row); 0 if cfg has no such launch
+int64_t s2_red_rows(const dm::ConvGeomSet& set, int ng, const dm::ConvCfg& c) {
+  if (!c.multi_merge_red) return 0;
+  long long mmax = 0;
+  for (int i = 0; i < ng; ++i) mmax = std::max(mmax, set.g[i].M);
+  return ng * ((mmax + c.rowtile - 1) / c.rowtile);
+}
+
+// part rows of a stride-2 3x3/p1 data gradient with the reduction epilogue (conv_dgrad red_part)
+int64_t dgrad_s2_red_rows(int64_t N, int64_t H, int64_t W, int64_t cfg) {
+  dm::ConvGeom base{};
+  base.N = N; base.OH = H; base.OW = W;
+  dm::ConvGeomSet set{};
+  bool any_empty;
+  const int ng = dgrad_s2_classes(base, 3, 3, 1, set, any_empty);
+  return s2_red_rows(set, ng, cfg_of(cfg));
+}
+
+// All parity classes in one launch: the pipelined tiles' (blockIdx.y = class), else the igemm
+// tile's (blockIdx.z = class); false when cfg has neither for this geometry
+bool launch_s2(const bf* dy, const bf* wd, bf* dx, const dm::ConvGeomSet& set, int ng,
+               const dm::ConvCfg& c, const bf* add, const dm::DgradSeg2* seg2,
+               const dm::BnBwdRed* red, hipStream_t st) {
+  if (ng <= 0) return false;
+  if (c.family == dm::ConvFamily::pipe &&
+      dm::conv_pipe_multi(dy, wd, dx, add, set, ng, c.id, st, seg2, red))
+    return true;
+  return dm::igemm_fwd_multi(dy, wd, dx, add, nullptr, set, ng, c.id, st, seg2, red);
 }
 
 // dx = conv_transpose(dy, w) for stride 1 or 2; add: tensor added to the result (may alias dx
@@ -152,11 +221,11 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
   // dy2 / wd2 (optional, stride 2): a 1x1/s2/p0 projection's output gradient and packed data-
   // gradient weights [Cin][1][1][C2]; its data gradient is merged into this launch (parity
   // class (0,0) gets a second K segment), so dx is written once, complete
-  // red_* (optional; stride 1: cfg 80, 90-93 or 42; stride 2: a complete data gradient on cfg
-  // 11-17 or 90-93): the backward reduction of the BatchNorm + ReLU whose output gradient dx is
-  // (its input red_y, forward scale/shift, mean/invstd, optionally the 1-bit red_mask instead
-  // of the mask from red_y) runs in this dgrad's epilogue -> red_part [rows][2][Cin]
-  // (bn_backward's pre_slab; rows = conv_stats_rows, stride 2: dgrad_s2_red_rows)
+  // red_* (optional; stride 1: a cfg with red_s1; stride 2: a complete data gradient on a cfg
+  // with multi_merge_red, csrc/conv_cfg.h): the backward reduction of the BatchNorm + ReLU whose
+  // output gradient dx is (its input red_y, forward scale/shift, mean/invstd, optionally the
+  // 1-bit red_mask instead of the mask from red_y) runs in this dgrad's epilogue -> red_part
+  // [rows][2][Cin] (bn_backward's pre_slab; rows = conv_stats_rows, stride 2: dgrad_s2_red_rows)
   // add_mask (optional, stride 1): 1-bit mask of `add` (bit j of byte i = element 8i + j), so
   // the identity-skip gradient dres = add * mask is added without being materialised
   need_bf16_nhwc(dy, "dy");
@@ -169,6 +238,7 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
   TORCH_CHECK(wd.scalar_type() == at::kBFloat16 && wd.numel() == (int64_t)Cin * KH * KW * Cout,
               "wd must be bf16 [Cin][KH][KW][Cout]");
   TORCH_CHECK(stride == 1 || stride == 2, "stride must be 1 or 2");
+  const dm::ConvCfg& c = cfg_of(cfg);
   const bf* addp = nullptr;
   if (add.has_value()) { need_bf16_nhwc(*add, "add"); TORCH_CHECK(add->sizes() == dx.sizes()); addp = bp(*add); }
   const bool accumulate = addp != nullptr;
@@ -176,10 +246,7 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
               "stride-2 dgrad accumulates only in place (add must alias dx)");
   const DeviceGuard guard(dy.device());
   auto st = cur_stream();
-  dm::ConvGeom base{};
-  base.N = N; base.H = OH; base.W = OW; base.C = Cout; base.lgC8 = ilog2(Cout / 8);
-  base.OH = H; base.OW = W; base.OC = Cin;
-  base.KW = KW; base.Ncols = Cin; base.wK = KH * KW * Cout;
+  const dm::ConvGeom base = dgrad_base(N, OH, OW, Cout, H, W, Cin, KH, KW);
   if (add_mask.has_value())
     TORCH_CHECK(addp && stride == 1 && addp != bp(dx),
                 "add_mask needs a separate add tensor and a stride-1 data gradient");
@@ -199,24 +266,20 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
                         fp(*red_shift), fp(*red_mean), fp(*red_invstd), fp(*red_part)};
   };
   if (stride == 1) {
-    auto g = base;
+    auto g = dgrad_s1_geom(base, KH, KW, pad);
     g.addm = addm;
-    g.Hg = H; g.Wg = W; g.isy = 1; g.isx = 1; g.osy = 1; g.osx = 1; g.oy0 = 0; g.ox0 = 0;
-    g.nth = KH; g.ntw = KW; g.dy0 = pad; g.dys = -1; g.dx0 = pad; g.dxs = -1;
-    g.kh0 = 0; g.khs = 1; g.kw0 = 0; g.kws = 1;
-    g.M = (long long)N * H * W; g.K = KH * KW * Cout;
-    dm::geom_finalize(g);
     if (red_y.has_value()) {
-      const bool pipe = cfg >= 90 && cfg <= 93 && dm::conv_pipe_supported(g, (int)cfg);
-      int hbn = 0, hwv = 0;
-      const bool halo = cfg == 42 && dm::halo_cfg((int)cfg, hbn, hwv) && dm::conv_halo_supported(g);
-      TORCH_CHECK(cfg == 80 || pipe || halo,
-                  "red_*: a cfg 80, pipelined (90-93) or cfg 42 data gradient");
-      const dm::BnBwdRed red = red_in(conv_stats_rows(g.M, cfg, Cin));
+      const bool pipe = c.family == dm::ConvFamily::pipe && dm::conv_pipe_supported(g, c.id);
+      const bool halo = c.family == dm::ConvFamily::halo && dm::conv_halo_supported(g);
+      TORCH_CHECK(c.red_s1 && (c.family == dm::ConvFamily::res64 || pipe || halo),
+                  "red_*: a cfg whose stride-1 launch has the reduction epilogue "
+                  "(csrc/conv_cfg.h red_s1), on a geometry its kernel covers");
+      const dm::BnBwdRed red = red_in(conv_stats_rows(g.M, cfg));
       if (pipe)
-        dm::conv_pipe(bp(dy), bp(wd), bp(dx), addp, nullptr, g, (int)cfg, st, &red);
+        dm::conv_pipe(bp(dy), bp(wd), bp(dx), addp, nullptr, g, c.id, st, &red);
       else if (halo)
-        dm::conv_halo(bp(dy), bp(wd), bp(dx), addp, nullptr, g, hbn, hwv, st, nullptr, nullptr, &red);
+        dm::conv_halo(bp(dy), bp(wd), bp(dx), addp, nullptr, g, c.bn, c.halo_waves, st, nullptr,
+                      nullptr, &red);
       else
         dm::conv_res64(bp(dy), bp(wd), bp(dx), addp, nullptr, g, st, nullptr, nullptr, &red);
       return;
@@ -224,45 +287,21 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
     dm::igemm_fwd(bp(dy), bp(wd), bp(dx), addp, nullptr, g, cfg, st);
     return;
   }
-  // parity classes write disjoint output pixels; a class with no taps (e.g. the odd
-  // pixels of a 1x1/s2 conv) is exactly zero, so zero-fill once up front when needed
-  bool any_empty = false;
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) {
-      const int kh0 = (a + pad) & 1, kw0 = (b + pad) & 1;
-      if ((KH - kh0 + 1) / 2 <= 0 || (KW - kw0 + 1) / 2 <= 0) any_empty = true;
-    }
+  dm::ConvGeomSet set{};
+  bool any_empty;
+  const int ng = dgrad_s2_classes(base, KH, KW, pad, set, any_empty);
+  // a class with no taps is exactly zero, so zero-fill once up front when needed
   if (any_empty && !accumulate)
     TORCH_CHECK(hipMemsetAsync(dx.data_ptr(), 0, dx.numel() * 2, st) == hipSuccess);
-  dm::ConvGeomSet set{};
-  int ng = 0;
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) {
-      auto g = base;
-      g.Hg = (H - a + 1) / 2; g.Wg = (W - b + 1) / 2;
-      if (g.Hg <= 0 || g.Wg <= 0) continue;
-      const int kh0 = (a + pad) & 1, kw0 = (b + pad) & 1;
-      const int nth = (KH - kh0 + 1) / 2, ntw = (KW - kw0 + 1) / 2;
-      if (nth <= 0 || ntw <= 0) continue;
-      g.isy = 1; g.isx = 1; g.osy = 2; g.osx = 2; g.oy0 = a; g.ox0 = b;
-      g.nth = nth; g.ntw = ntw;
-      g.dy0 = (a + pad - kh0) / 2; g.dys = -1; g.dx0 = (b + pad - kw0) / 2; g.dxs = -1;
-      g.kh0 = kh0; g.khs = 2; g.kw0 = kw0; g.kws = 2;
-      g.M = (long long)N * g.Hg * g.Wg; g.K = nth * ntw * Cout;
-      dm::geom_finalize(g);
-      set.g[ng++] = g;
-    }
-  const bool multi_igemm = cfg == 11 || cfg == 12 || cfg == 13 || cfg == 14 || cfg == 15 ||
-                           cfg == 16 || cfg == 17;
-  // the pipelined tiles merge a projection of dy's own channel count (ResNet: always)
-  const bool multi_pipe = cfg >= 90 && cfg <= 93;
   dm::DgradSeg2 seg2{};
   const bool merged = dy2.has_value();
   if (merged) {
-    TORCH_CHECK((multi_igemm || (multi_pipe && dy2->size(3) == Cout)) && !accumulate && ng == 4 &&
-                    pad == 1 && KH == 3 && KW == 3,
-                "dy2: a 3x3/s2/p1 data gradient on an igemm tile (cfg 11-17) or a pipelined tile "
-                "(cfg 90-93, projection channels == dy's), no add");
+    // (the pipelined tiles merge a projection of dy's own channel count: ResNet's always is)
+    TORCH_CHECK(c.multi_merge_red && (!c.merge_same_c || dy2->size(3) == Cout) && !accumulate &&
+                    ng == 4 && pad == 1 && KH == 3 && KW == 3,
+                "dy2: a 3x3/s2/p1 data gradient on a cfg with a merged multi-geometry launch "
+                "(csrc/conv_cfg.h multi_merge_red; merge_same_c: projection channels == dy's), "
+                "no add");
     need_bf16_nhwc(*dy2, "dy2");
     TORCH_CHECK(dy2->size(0) == N && dy2->size(1) == OH && dy2->size(2) == OW && dy2->size(3) % 64 == 0,
                 "dy2: [N, OH, OW, C2] with dy's grid, C2 % 64 == 0");
@@ -272,8 +311,8 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
     // the kernels address both through 32-bit buffer ranges (x2bytes / w2bytes below)
     TORCH_CHECK(dy2->numel() * 2 < (1LL << 31) && wd2->numel() * 2 < (1LL << 31),
                 "dy2 / wd2: each must be below 2 GiB");
-    // class (a, b) = (0, 0) is geometry 0 (the a-major loop above): rows (y, x) are the output
-    // pixels (2y, 2x), read dY at (y, x) through the centre tap -- the 1x1/s2/p0 map
+    // class (a, b) = (0, 0) is geometry 0 (a-major): rows (y, x) are the output pixels
+    // (2y, 2x), read dY at (y, x) through the centre tap -- the 1x1/s2/p0 map
     TORCH_CHECK(set.g[0].oy0 == 0 && set.g[0].ox0 == 0 && set.g[0].Hg == OH && set.g[0].Wg == OW,
                 "dy2: parity class (0,0) must cover dy's grid");
     seg2.X2 = dy2->data_ptr();
@@ -283,38 +322,21 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
     seg2.C2 = (int)dy2->size(3);
     seg2.z = 0;
   }
+  dm::BnBwdRed red{};
   if (red_y.has_value()) {
-    TORCH_CHECK((multi_igemm || multi_pipe) && !accumulate && !any_empty && ng == 4,
+    TORCH_CHECK(c.multi_merge_red && !accumulate && !any_empty && ng == 4,
                 "red_* with stride 2: a complete data gradient (all 4 parity classes, no add) on "
-                "an igemm (cfg 11-17) or pipelined (cfg 90-93) tile");
-    const dm::BnBwdRed red = red_in(multi_pipe ? dm::pipe_multi_rows(set, ng)
-                                               : dm::igemm_multi_rows(set, ng, (int)cfg));
-    const bool ok = multi_pipe
-        ? dm::conv_pipe_multi(bp(dy), bp(wd), bp(dx), nullptr, set, ng, (int)cfg, st,
-                              merged ? &seg2 : nullptr, &red)
-        : dm::igemm_fwd_multi(bp(dy), bp(wd), bp(dx), nullptr, nullptr, set, ng, (int)cfg, st,
-                              merged ? &seg2 : nullptr, &red);
-    TORCH_CHECK(ok, "stride-2 dgrad with reduction: unsupported cfg / geometry");
-    return;
+                "a cfg with a reducing multi-geometry launch (csrc/conv_cfg.h multi_merge_red)");
+    red = red_in(s2_red_rows(set, ng, c));
   }
-  if (merged) {
-    const bool ok = multi_pipe
-        ? dm::conv_pipe_multi(bp(dy), bp(wd), bp(dx), nullptr, set, ng, (int)cfg, st, &seg2, nullptr)
-        : dm::igemm_fwd_multi(bp(dy), bp(wd), bp(dx), nullptr, nullptr, set, ng, (int)cfg, st, &seg2,
-                              nullptr);
-    TORCH_CHECK(ok, "merged stride-2 dgrad: unsupported cfg / geometry");
+  const bf* acc = accumulate ? bp(dx) : nullptr;
+  const bool special = merged || red_y.has_value();
+  if (launch_s2(bp(dy), bp(wd), bp(dx), set, ng, c, acc, merged ? &seg2 : nullptr,
+                red_y.has_value() ? &red : nullptr, st))
     return;
-  }
-  // pipelined tiles: all parity classes in one launch (blockIdx.y = class)
-  if (cfg >= 90 && cfg <= 93 && ng > 0 &&
-      dm::conv_pipe_multi(bp(dy), bp(wd), bp(dx), accumulate ? bp(dx) : nullptr, set, ng, (int)cfg, st))
-    return;
-  // all parity classes in one launch (blockIdx.z = class) when the tile supports it
-  if (ng > 0 && dm::igemm_fwd_multi(bp(dy), bp(wd), bp(dx), accumulate ? bp(dx) : nullptr, nullptr,
-                                    set, ng, (int)cfg, st))
-    return;
+  TORCH_CHECK(!special, "merged / reducing stride-2 dgrad: unsupported cfg / geometry");
   for (int i = 0; i < ng; ++i)
-    dm::igemm_fwd(bp(dy), bp(wd), bp(dx), accumulate ? bp(dx) : nullptr, nullptr, set.g[i], cfg, st);
+    dm::igemm_fwd(bp(dy), bp(wd), bp(dx), acc, nullptr, set.g[i], cfg, st);
 }
 
 // dw (fp32 OIHW [Cout][Cin][KH][KW]) = beta*dw + Σ_m dy ⊗ im2col(x)
@@ -339,13 +361,15 @@ void conv_wgrad(at::Tensor x, at::Tensor dy, at::Tensor dw, at::Tensor slab, int
     // x = previous conv's raw output, operand relu(x*sc + sh)
     TORCH_CHECK(pre_shift.has_value() && !s2d, "pre_scale needs pre_shift (not with s2d)");
     const auto [psc, psh] = pre_bn(pre_scale, pre_shift, x);
-    if (cfg == 8) {
+    const dm::WgradCfg* wc = dm::wgrad_cfg((int)cfg);
+    const bool res64 = wc && wc->family == dm::WgradFamily::res64;
+    TORCH_CHECK(wc && wc->pre_bn && (res64 || dm::wgrad_halo_supported(g)),
+                "fused pre-BN needs a wgrad cfg that stages it (csrc/conv_cfg.h pre_bn) and, for "
+                "the halo kernel, a 3x3/s1/p1 geometry");
+    if (res64)
       dm::wgrad_res64(bp(x), bp(dy), fp(slab), g, (int)S, st, psc, psh);
-    } else {
-      TORCH_CHECK((cfg == 4 || cfg == 5) && dm::wgrad_halo_supported(g),
-                  "fused pre-BN needs the halo wgrad (cfg 4/5/8) and a 3x3/s1/p1 geometry");
-      dm::wgrad_halo(bp(x), bp(dy), fp(slab), g, (int)S, mchunk, cfg == 4 ? 3 : 1, st, psc, psh);
-    }
+    else
+      dm::wgrad_halo(bp(x), bp(dy), fp(slab), g, (int)S, mchunk, wc->taps / 3, st, psc, psh);
   } else {
     dm::igemm_wgrad(bp(x), bp(dy), fp(slab), g, (int)S, mchunk, cfg, st);
   }
@@ -403,7 +427,6 @@ void pack_weights(at::Tensor w, at::Tensor wf, c10::optional<at::Tensor> wd, int
   dm::pack_weights(fp(w), bp(wf), wdp, Cout, Cin, Cpad, KH, KW, cur_stream());
 }
 
-// ------------------------------------------------------------------ BN
 // LDS-tiled variant: tprefix[l] = first 32x32 (co, ci) tile of layer l
 void pack_weights_tiled(at::Tensor desc, at::Tensor tprefix, int64_t ntiles) {
   TORCH_CHECK(desc.is_cuda() && tprefix.is_cuda() && desc.scalar_type() == at::kLong &&
@@ -416,6 +439,7 @@ void pack_weights_tiled(at::Tensor desc, at::Tensor tprefix, int64_t ntiles) {
                          cur_stream());
 }
 
+// ------------------------------------------------------------------ BN
 void bn_stats_finalize(at::Tensor stats, int64_t T, double count, at::Tensor gamma, at::Tensor beta,
                        c10::optional<at::Tensor> rmean, c10::optional<at::Tensor> rvar,
                        double momentum, double eps, at::Tensor scale, at::Tensor shift,
@@ -821,11 +845,26 @@ void stem_pack_weights(at::Tensor w, at::Tensor wk) {
   dm::stem_pack_weights(fp(w), bp(wk), cur_stream());
 }
 
+// a row of csrc/conv_cfg.h as a dict; None for an id the table does not have
+template <class Row>
+py::object cfg_dict(const Row* c) {
+  if (!c) return py::none();
+  py::dict d;
+  dm::cfg_fields(*c, [&](const char* k, auto v) { d[k] = v; });
+  return d;
+}
+py::object conv_cfg_info(int64_t cfg) { return cfg_dict(dm::conv_cfg((int)cfg)); }
+py::object wgrad_cfg_info(int64_t cfg) { return cfg_dict(dm::wgrad_cfg((int)cfg)); }
+
 void register_resnet(pybind11::module_& m) {
   m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("wpack"), py::arg("y"), py::arg("stats"),
         py::arg("add"), py::arg("KH"), py::arg("KW"), py::arg("stride"), py::arg("pad"),
         py::arg("cfg"), py::arg("pre_scale") = py::none(), py::arg("pre_shift") = py::none());
-  m.def("conv_stats_rows", &conv_stats_rows, py::arg("M"), py::arg("cfg"), py::arg("ncols") = -1);
+  // ncols: unused; still accepted from the callers that pass it
+  m.def("conv_stats_rows", [](int64_t M, int64_t cfg, int64_t) { return conv_stats_rows(M, cfg); },
+        py::arg("M"), py::arg("cfg"), py::arg("ncols") = -1);
+  m.def("conv_cfg_info", &conv_cfg_info, py::arg("cfg"));
+  m.def("wgrad_cfg_info", &wgrad_cfg_info, py::arg("cfg"));
   m.def("conv_dgrad", &conv_dgrad, py::arg("dy"), py::arg("wd"), py::arg("dx"), py::arg("KH"),
         py::arg("KW"), py::arg("stride"), py::arg("pad"),
         py::arg("add") = py::none(), py::arg("cfg") = 12, py::arg("add_mask") = py::none(),

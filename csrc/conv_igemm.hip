@@ -28,6 +28,7 @@
 // The reduction is split over blocks into fp32 slabs and combined by a fixed-order
 // reduce that also permutes to the OIHW fp32 gradient layout and applies beta.
 #include "common.h"
+#include "conv_cfg.h"
 #include "conv_geom.h"
 #include "igemm_common.h"
 #include "kernels.h"
@@ -725,161 +726,107 @@ static void launch_fwd3_set(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const 
   k<<<grid, WM * WN * 64, sm, st>>>(X, Wp, Y, ADD, stats, gs, xb, wb, s2, rd);
 }
 
-// the multi-geometry launch with the optional merged segment / reduction epilogue variants
-template <int BM, int BN, int WM, int WN, bool MF32, int DEPTH>
-static void launch_fwd3_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
-                              float* stats, const ConvGeomSet& gs, int ng, hipStream_t st,
-                              const DgradSeg2* seg2, const BnBwdRed* red) {
-  if (seg2 && red)
-    launch_fwd3_set<BM, BN, WM, WN, MF32, DEPTH, true, true>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red);
-  else if (seg2)
-    launch_fwd3_set<BM, BN, WM, WN, MF32, DEPTH, true, false>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red);
-  else if (red)
-    launch_fwd3_set<BM, BN, WM, WN, MF32, DEPTH, false, true>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red);
-  else
-    launch_fwd3_set<BM, BN, WM, WN, MF32, DEPTH>(X, Wp, Y, ADD, stats, gs, ng, st);
-}
-
-template <int BM, int BN, int WM, int WN, bool MF32, int DEPTH>
-static void launch_fwd3(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
-                        float* stats, const ConvGeom& g, hipStream_t st) {
-  launch_fwd3_set<BM, BN, WM, WN, MF32, DEPTH>(X, Wp, Y, ADD, stats, ConvGeomSet::one(g), 1,
-                                               st);
+// kConvCfgs[I] of an igemm row: igemm_fwd3_kernel's template arguments come from the table
+template <size_t I, bool SEG2 = false, bool RED = false>
+static void launch_fwd3_row(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
+                            float* stats, const ConvGeomSet& gs, int ng, hipStream_t st,
+                            const DgradSeg2* seg2 = nullptr, const BnBwdRed* red = nullptr) {
+  constexpr ConvCfg c = kConvCfgs[I];
+  launch_fwd3_set<c.bm, c.bn, c.wm, c.wn, c.mf32, c.depth, SEG2, RED>(X, Wp, Y, ADD, stats, gs, ng,
+                                                                       st, seg2, red);
 }
 
 // up to four geometries sharing X / W / Y (the parity classes of a stride-2 dgrad) in one
-// launch on the v3 128x128 mf32 tile (no statistics: the classes' row tiles would collide)
+// launch of a tile that has one (no statistics: the classes' row tiles would collide).  The
+// merged-segment / reduction-epilogue variants exist only for the rows that say so
 bool igemm_fwd_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
                      const ConvGeomSet& gs, int ng, int cfg, hipStream_t st, const DgradSeg2* seg2,
                      const BnBwdRed* red) {
   if (seg2 && (seg2->C2 % 64 != 0 || seg2->z < 0 || seg2->z >= ng))
     throw std::runtime_error("igemm_fwd_multi: seg2 needs C2 % 64 == 0 and a valid geometry");
-  switch (cfg) {  // the v3 mf32 tiles of igemm_fwd (12/13: one tile of prefetch, 15/16: two)
-    case 12: launch_fwd3_multi<128, 128, 2, 2, true, 1>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red); return true;
-    case 13: launch_fwd3_multi<128, 64, 2, 2, true, 1>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red); return true;
-    case 15: launch_fwd3_multi<128, 128, 2, 2, true, 2>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red); return true;
-    case 16: launch_fwd3_multi<128, 64, 2, 2, true, 2>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red); return true;
-    // the 64x64 16x16x32 tiles (small grids: few images per GPU)
-    case 11: case 14: launch_fwd3_multi<64, 64, 2, 2, false, 1>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red); return true;
-    case 17: launch_fwd3_multi<64, 64, 2, 2, false, 2>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red); return true;
-    default: return false;
-  }
+  bool done = false;
+  with_cfg_row<kConvCfgs, ConvFamily::igemm>(cfg, [&](auto row) {
+    constexpr size_t I = decltype(row)::value;
+    if constexpr (kConvCfgs[I].multi_merge_red) {
+      if (seg2 && red) launch_fwd3_row<I, true, true>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red);
+      else if (seg2) launch_fwd3_row<I, true, false>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red);
+      else if (red) launch_fwd3_row<I, false, true>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red);
+      else launch_fwd3_row<I>(X, Wp, Y, ADD, stats, gs, ng, st);
+      done = true;
+    } else if constexpr (kConvCfgs[I].multi) {
+      if (!seg2 && !red) {
+        launch_fwd3_row<I>(X, Wp, Y, ADD, stats, gs, ng, st);
+        done = true;
+      }
+    }
+  });
+  return done;
 }
 
-// part rows of a multi-geometry launch with the BN-backward reduction epilogue (blockIdx.z
-// major, blockIdx.x minor; every block writes its row)
-long long igemm_multi_rows(const ConvGeomSet& gs, int ng, int cfg) {
-  long long mmax = 0;
-  for (int i = 0; i < ng; ++i) mmax = gs.g[i].M > mmax ? gs.g[i].M : mmax;
-  const int bm = (cfg == 12 || cfg == 13 || cfg == 15 || cfg == 16) ? 128
-                 : (cfg == 11 || cfg == 14 || cfg == 17) ? 64 : 0;
-  if (!bm) return 0;
-  return (long long)ng * ((mmax + bm - 1) / bm);
-}
-
-// halo-kernel configs (conv_halo.hip): 42 = 128-pixel tile of 2 x 2 waves, BN 128, with
-// two weight tiles of register prefetch (waves bit 8); 39 = 256-pixel tile of 4 x 2 waves,
-// BN 64; 41 = 256-pixel tile of 4 x 1 waves of 64 x 64.  (The round-2 tiles 20 / 21, 42
-// without the prefetch and BN 64, lost on every layer and are removed.)
-int igemm_fwd_rowtile(int cfg);
-bool halo_cfg(int cfg, int& bn, int& waves) {
-  switch (cfg) {
-    case 42: bn = 128; waves = 4 | 0x100; return true;
-    case 39: bn = 64; waves = 16; return true;
-    case 41: bn = 64; waves = 32; return true;
-    default: return false;
-  }
-}
-
-// Forward-style conv GEMM (forward, stride-1 dgrad, one dgrad parity class), by cfg:
-//   9 / 10 / 11  v3 tiles 128x128 / 128x64 / 64x64 (2 x 2 waves) on 16x16x32 MFMA
-//   12 / 13 / 14 the same on 32x32x16 MFMA (64x64 as 16x16x32: 14 == 11)
-//   15 / 16 / 17 12 / 13 / 11 with two tiles of register prefetch
-//   20 / 21 / 42 / 39 / 41  halo-staged unit-stride tiles (conv_halo.hip, see halo_cfg)
-//   60           space-to-depth stem kernel (conv_stem.hip)
-//   80           persistent resident-weight 64 -> 64 channel 3x3 conv (conv_res64.hip)
-//   90 - 93      pipelined LDS-DMA tiles (conv_pipe.hip)
-// Shapes a specialised kernel does not cover fall back to a v3 tile with the same row tile,
-// so the statistics slab rows (igemm_fwd_rowtile) still match.
+// Forward-style conv GEMM (forward, stride-1 dgrad, one dgrad parity class) on the kernel
+// conv_cfg.h lists for cfg.  A geometry the specialised kernel does not cover runs on the row's
+// fallback igemm tile, which has the same row tile, so the statistics slab rows still match.
 void igemm_fwd(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
                const ConvGeom& g, int cfg, hipStream_t st) {
-  if (cfg >= 90 && cfg <= 93) {
-    if (conv_pipe_supported(g, cfg)) return conv_pipe(X, Wp, Y, ADD, stats, g, cfg, st);
-    if (g.Ncols % 128 == 0) return launch_fwd3<256, 128, 4, 2, true, 1>(X, Wp, Y, ADD, stats, g, st);
-    return launch_fwd3<256, 64, 4, 2, true, 1>(X, Wp, Y, ADD, stats, g, st);
+  const ConvCfg* c = conv_cfg(cfg);
+  if (!c) throw std::runtime_error("igemm_fwd: unknown cfg " + std::to_string(cfg));
+  switch (c->family) {
+    case ConvFamily::pipe:
+      if (conv_pipe_supported(g, cfg)) return conv_pipe(X, Wp, Y, ADD, stats, g, cfg, st);
+      break;
+    case ConvFamily::res64:
+      return conv_res64(X, Wp, Y, ADD, stats, g, st);  // throws if unsupported
+    case ConvFamily::stem:
+      if (!ADD && stem_conv_supported(g)) return stem_conv(X, Wp, Y, stats, g, st);
+      break;
+    case ConvFamily::halo:
+      if (conv_halo_supported(g))
+        return conv_halo(X, Wp, Y, ADD, stats, g, c->bn, c->halo_waves, st);
+      break;
+    case ConvFamily::igemm:
+      break;
   }
-  if (cfg == 80) return conv_res64(X, Wp, Y, ADD, stats, g, st);  // throws if unsupported
-  if (cfg == 60) {
-    if (!ADD && stem_conv_supported(g)) return stem_conv(X, Wp, Y, stats, g, st);
-    return launch_fwd3<256, 64, 4, 2, true, 1>(X, Wp, Y, ADD, stats, g, st);
-  }
-  int bn, waves;
-  if (halo_cfg(cfg, bn, waves)) {
-    if (conv_halo_supported(g)) return conv_halo(X, Wp, Y, ADD, stats, g, bn, waves, st);
-    if (igemm_fwd_rowtile(cfg) == 256) {
-      if (bn == 128) return launch_fwd3<256, 128, 4, 2, true, 1>(X, Wp, Y, ADD, stats, g, st);
-      return launch_fwd3<256, 64, 4, 2, true, 1>(X, Wp, Y, ADD, stats, g, st);
-    }
-    cfg = bn == 128 ? 12 : 13;
-  }
-  switch (cfg) {
-    case 9: return launch_fwd3<128, 128, 2, 2, false, 1>(X, Wp, Y, ADD, stats, g, st);
-    case 10: return launch_fwd3<128, 64, 2, 2, false, 1>(X, Wp, Y, ADD, stats, g, st);
-    case 11: case 14: return launch_fwd3<64, 64, 2, 2, false, 1>(X, Wp, Y, ADD, stats, g, st);
-    case 12: return launch_fwd3<128, 128, 2, 2, true, 1>(X, Wp, Y, ADD, stats, g, st);
-    case 13: return launch_fwd3<128, 64, 2, 2, true, 1>(X, Wp, Y, ADD, stats, g, st);
-    case 15: return launch_fwd3<128, 128, 2, 2, true, 2>(X, Wp, Y, ADD, stats, g, st);
-    case 16: return launch_fwd3<128, 64, 2, 2, true, 2>(X, Wp, Y, ADD, stats, g, st);
-    case 17: return launch_fwd3<64, 64, 2, 2, false, 2>(X, Wp, Y, ADD, stats, g, st);
-    default: throw std::runtime_error("igemm_fwd: unknown cfg " + std::to_string(cfg));
-  }
+  const int tile = c->family == ConvFamily::igemm ? cfg : cfg_fallback(*c, g.Ncols);
+  with_cfg_row<kConvCfgs, ConvFamily::igemm>(tile, [&](auto row) {
+    launch_fwd3_row<decltype(row)::value>(X, Wp, Y, ADD, stats, ConvGeomSet::one(g), 1, st);
+  });
 }
 
-int igemm_fwd_rowtile(int cfg) {
-  if ((cfg >= 90 && cfg <= 93) || cfg == 60 || cfg == 39 || cfg == 41) return 256;
-  return (cfg == 11 || cfg == 14 || cfg == 17) ? 64 : 128;
-}
-
-void igemm_wgrad(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
-                 long long mchunk, int cfg, hipStream_t st) {
+template <int BM, int BK>
+static void launch_wgrad2(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
+                          long long mchunk, hipStream_t st) {
   const unsigned xb = (unsigned)((long long)g.N * g.H * g.W * g.C * 2);
   const unsigned db = (unsigned)(g.M * g.Ncols * 2);
-  // 8: row-streaming 64 -> 64 channel 3x3 kernel (wgrad_res64.hip), one slab per workgroup;
-  // 4 / 5: halo-staged 3x3 unit-stride kernel (wgrad_halo.hip) with 9 / 3 taps per block;
-  // other shapes fall back to the v2 tiles: 2 = 128x128, 3 = 64x128, 6 = 64x256
-  if (cfg == 8) return wgrad_res64(X, DY, slab, g, S, st);  // throws if unsupported
-  // 7: stride-2 parity-plane kernel (wgrad_halo.hip), 3x3 only (other shapes: v2 tiles)
-  if (cfg == 7) {
-    if (wgrad_s2_supported(g)) return wgrad_s2(X, DY, slab, g, S, mchunk, st);
-    cfg = g.Ncols % 128 == 0 ? 2 : 3;
+  dim3 grid((g.Ncols + BM - 1) / BM, (g.K + BK - 1) / BK, S);
+  auto k = igemm_wgrad2_kernel<BM, BK, 2, 2>;
+  const size_t sm = 2 * 64 * ((BM + 16) + (BK + 16)) * 2 + MAXTAPS * 16;
+  set_smem_attr(k, sm);
+  k<<<grid, 256, sm, st>>>(X, DY, slab, g, mchunk, xb, db);
+}
+
+// Weight gradient on the kernel conv_cfg.h lists for cfg; a geometry the halo / stride-2
+// kernel does not cover runs on the row's fallback v2 tile
+void igemm_wgrad(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
+                 long long mchunk, int cfg, hipStream_t st) {
+  const WgradCfg* c = wgrad_cfg(cfg);
+  if (!c) throw std::runtime_error("igemm_wgrad: unknown cfg " + std::to_string(cfg));
+  switch (c->family) {
+    case WgradFamily::res64:
+      return wgrad_res64(X, DY, slab, g, S, st);  // throws if unsupported
+    case WgradFamily::s2:
+      if (wgrad_s2_supported(g)) return wgrad_s2(X, DY, slab, g, S, mchunk, st);
+      break;
+    case WgradFamily::halo:
+      if (wgrad_halo_supported(g)) return wgrad_halo(X, DY, slab, g, S, mchunk, c->taps / 3, st);
+      break;
+    case WgradFamily::v2:
+      break;
   }
-  if (cfg == 4 || cfg == 5) {
-    if (wgrad_halo_supported(g)) return wgrad_halo(X, DY, slab, g, S, mchunk, cfg == 4 ? 3 : 1, st);
-    cfg = g.Ncols % 128 == 0 ? 2 : 3;
-  }
-  if (cfg != 2 && cfg != 3 && cfg != 6)
-    throw std::runtime_error("igemm_wgrad: cfg must be 2, 3, 4, 5 or 6");
-  if (cfg == 2) {
-    dim3 grid((g.Ncols + 127) / 128, (g.K + 127) / 128, S);
-    auto k = igemm_wgrad2_kernel<128, 128, 2, 2>;
-    const size_t sm = 2 * 64 * ((128 + 16) + (128 + 16)) * 2 + MAXTAPS * 16;
-    set_smem_attr(k, sm);
-    k<<<grid, 256, sm, st>>>(X, DY, slab, g, mchunk, xb, db);
-  } else if (cfg == 6) {
-    // 64 x 256: the whole K of the s2d stem (4x4 taps x 16 ch) in one tile, so every dY
-    // row is read once instead of once per 128-column K tile
-    dim3 grid((g.Ncols + 63) / 64, (g.K + 255) / 256, S);
-    auto k = igemm_wgrad2_kernel<64, 256, 2, 2>;
-    const size_t sm = 2 * 64 * ((64 + 16) + (256 + 16)) * 2 + MAXTAPS * 16;
-    set_smem_attr(k, sm);
-    k<<<grid, 256, sm, st>>>(X, DY, slab, g, mchunk, xb, db);
-  } else {
-    dim3 grid((g.Ncols + 63) / 64, (g.K + 127) / 128, S);
-    auto k = igemm_wgrad2_kernel<64, 128, 2, 2>;
-    const size_t sm = 2 * 64 * ((64 + 16) + (128 + 16)) * 2 + MAXTAPS * 16;
-    set_smem_attr(k, sm);
-    k<<<grid, 256, sm, st>>>(X, DY, slab, g, mchunk, xb, db);
-  }
+  const int tile = c->family == WgradFamily::v2 ? cfg : cfg_fallback(*c, g.Ncols);
+  with_cfg_row<kWgradCfgs, WgradFamily::v2>(tile, [&](auto row) {
+    constexpr WgradCfg t = kWgradCfgs[decltype(row)::value];
+    launch_wgrad2<t.bm, t.bk>(X, DY, slab, g, S, mchunk, st);
+  });
 }
 
 void wgrad_reduce(const float* slab, int S, int Cout, int C, int Cin, int KH, int KW, float* dw,

@@ -30,6 +30,7 @@
 // swz), conflict-free for the 32x32x16 fragment reads; the DMA image is lane-linear (base +
 // 16 * lane), so the swizzle is applied to the SOURCE chunk each lane fetches.
 #include "common.h"
+#include "conv_cfg.h"
 #include "conv_geom.h"
 #include "igemm_common.h"
 #include "kernels.h"
@@ -544,18 +545,22 @@ void launch_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD
   DM_CHECK(hipGetLastError());
 }
 
-template <int BN, int WM, int WN, int MINW>
-void launch_pipe1(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-                  const ConvGeom& g, hipStream_t st, const BnBwdRed* red) {
-  launch_pipe<BN, WM, WN, MINW>(X, Wp, Y, ADD, stats, ConvGeomSet::one(g), 1, st, red);
+// launch_pipe on the tile of a pipe row of conv_cfg.h; false for any other cfg
+bool launch_pipe_cfg(int cfg, const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
+                     float* stats, const ConvGeomSet& gs, int ng, hipStream_t st,
+                     const BnBwdRed* red, const DgradSeg2* seg2) {
+  return with_cfg_row<kConvCfgs, ConvFamily::pipe>(cfg, [&](auto row) {
+    constexpr ConvCfg c = kConvCfgs[decltype(row)::value];
+    static_assert(c.bm == PBM, "the pipe kernels' row tile");
+    launch_pipe<c.bn, c.wm, c.wn, c.minw>(X, Wp, Y, ADD, stats, gs, ng, st, red, seg2);
+  });
 }
 }  // namespace
 
-int pipe_bn(int cfg) { return cfg == 90 ? 256 : cfg == 93 ? 64 : 128; }
-
 bool conv_pipe_supported(const ConvGeom& g, int cfg) {
-  const int bn = pipe_bn(cfg);
-  if (g.C % PBK != 0 || g.nth * g.ntw > 32 || g.Ncols % bn != 0) return false;
+  const ConvCfg* c = conv_cfg(cfg);
+  if (!c || c->family != ConvFamily::pipe) return false;
+  if (g.C % PBK != 0 || g.nth * g.ntw > 32 || g.Ncols % c->bn != 0) return false;
   if ((long long)g.N * g.H * g.W * g.C * 2 >= (1LL << 31)) return false;
   if ((long long)g.Ncols * g.wK * 2 >= (1LL << 31)) return false;
   if (g.M >= (1LL << 31) || g.C > 2048) return false;
@@ -564,13 +569,8 @@ bool conv_pipe_supported(const ConvGeom& g, int cfg) {
 
 void conv_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
                const ConvGeom& g, int cfg, hipStream_t st, const BnBwdRed* red) {
-  // 90: 256 x 256, 8 waves (2 x 4) of 128 x 64; 91: 256 x 128, 8 waves (4 x 2) of 64 x 64;
-  // 92: 256 x 128, 4 waves (2 x 2) of 128 x 64; 93: 256 x 64, 4 waves (4 x 1) of 64 x 64,
-  // two workgroups per CU (80 KB of LDS each)
-  if (cfg == 90) launch_pipe1<256, 2, 4, 1>(X, Wp, Y, ADD, stats, g, st, red);
-  else if (cfg == 91) launch_pipe1<128, 4, 2, 1>(X, Wp, Y, ADD, stats, g, st, red);
-  else if (cfg == 92) launch_pipe1<128, 2, 2, 1>(X, Wp, Y, ADD, stats, g, st, red);
-  else launch_pipe1<64, 4, 1, 2>(X, Wp, Y, ADD, stats, g, st, red);
+  if (!launch_pipe_cfg(cfg, X, Wp, Y, ADD, stats, ConvGeomSet::one(g), 1, st, red, nullptr))
+    throw std::runtime_error("conv_pipe: not a pipelined cfg");
 }
 
 // the parity classes of a stride-2 data gradient (no statistics) in one launch
@@ -581,18 +581,7 @@ bool conv_pipe_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t*
   for (int i = 0; i < ng; ++i)
     if (!conv_pipe_supported(gs.g[i], cfg)) return false;
   if (seg2 && seg2->C2 != gs.g[0].C) return false;
-  if (cfg == 90) launch_pipe<256, 2, 4, 1>(X, Wp, Y, ADD, nullptr, gs, ng, st, red, seg2);
-  else if (cfg == 91) launch_pipe<128, 4, 2, 1>(X, Wp, Y, ADD, nullptr, gs, ng, st, red, seg2);
-  else if (cfg == 92) launch_pipe<128, 2, 2, 1>(X, Wp, Y, ADD, nullptr, gs, ng, st, red, seg2);
-  else launch_pipe<64, 4, 1, 2>(X, Wp, Y, ADD, nullptr, gs, ng, st, red, seg2);
-  return true;
-}
-
-// part rows of a multi-geometry pipelined launch with the reduction epilogue
-long long pipe_multi_rows(const ConvGeomSet& gs, int ng) {
-  long long mmax = 0;
-  for (int i = 0; i < ng; ++i) mmax = gs.g[i].M > mmax ? gs.g[i].M : mmax;
-  return (long long)ng * ((mmax + PBM - 1) / PBM);
+  return launch_pipe_cfg(cfg, X, Wp, Y, ADD, nullptr, gs, ng, st, red, seg2);
 }
 
 }  // namespace dm

@@ -101,18 +101,17 @@ void p2p_xgmi_send(const void* src, long long bytes, void* ring, void* full, con
                    long long slot_bytes, int nslot, unsigned* state, hipStream_t st);
 void p2p_xgmi_recv(void* dst, long long bytes, const void* ring, const void* full, void* free_,
                    long long slot_bytes, int nslot, unsigned* state, hipStream_t st);
-// conv_igemm.hip
+// conv_igemm.hip; every `cfg` below is an id of csrc/conv_cfg.h
 struct ConvGeom;
 struct ConvGeomSet;
 struct DgradSeg2;
 struct BnBwdRed;
 // seg2 (optional): a second K segment of geometry seg2->z (a 1x1/s2 projection's data
 // gradient merged into the stride-2 dgrad's parity class (0,0)); red (optional): the consumer
-// BatchNorm's backward sums in the epilogue (one part row per block: igemm_multi_rows)
+// BatchNorm's backward sums in the epilogue (one part row per block, class-major)
 bool igemm_fwd_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
                      const ConvGeomSet& gs, int ng, int cfg, hipStream_t st,
                      const DgradSeg2* seg2 = nullptr, const BnBwdRed* red = nullptr);
-long long igemm_multi_rows(const ConvGeomSet& gs, int ng, int cfg);
 void igemm_fwd(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
                const ConvGeom& g, int cfg, hipStream_t st);
 // conv_stem.hip: s2d stem (16 channels, 16 taps, 64 outputs) with resident weights (cfg 60)
@@ -164,7 +163,6 @@ bool conv_pipe_supported(const ConvGeom& g, int cfg);
 bool conv_pipe_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
                      const ConvGeomSet& gs, int ng, int cfg, hipStream_t st,
                      const DgradSeg2* seg2 = nullptr, const BnBwdRed* red = nullptr);
-long long pipe_multi_rows(const ConvGeomSet& gs, int ng);
 void conv_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
                const ConvGeom& g, int cfg, hipStream_t st, const BnBwdRed* red = nullptr);
 // conv_res64.hip: persistent register-resident-weight 3x3 conv, 64 -> 64 channels (cfg 80);
@@ -174,8 +172,8 @@ int res64_grid(long long M);
 void conv_res64(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
                 const ConvGeom& g, hipStream_t st, const float* pre_sc = nullptr,
                 const float* pre_sh = nullptr, const BnBwdRed* red = nullptr);
+// conv_halo.hip: halo-staged unit-stride tiles; bn / waves = the row's bn / halo_waves (conv_cfg.h)
 bool conv_halo_supported(const ConvGeom& g);
-bool halo_cfg(int cfg, int& bn, int& waves);
 void conv_halo(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
                const ConvGeom& g, int bn, int waves, hipStream_t st,
                const float* pre_sc = nullptr, const float* pre_sh = nullptr,
@@ -194,7 +192,6 @@ void wgrad_halo(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& 
                 const float* pre_sh = nullptr);
 void pack_weights_tiled(const long long* desc, const int* tprefix, int nl, int ntiles,
                         hipStream_t st);
-int igemm_fwd_rowtile(int cfg);
 void igemm_wgrad(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
                  long long mchunk, int cfg, hipStream_t st);
 void wgrad_reduce(const float* slab, int S, int Cout, int C, int Cin, int KH, int KW, float* dw,
@@ -221,7 +218,6 @@ void bn_backward(const bf16_t* dout, const bf16_t* out, const bf16_t* y, const f
 void bn_relu_maxpool(const bf16_t* y, const float* scale, const float* shift, bf16_t* out,
                      uint8_t* idx, int N, int H, int W, int C, int OH, int OW, int K, int S,
                      int P, hipStream_t st, bf16_t* yarg = nullptr);
-int bn_bwd_groups(long long M, int C);
 int bn_bwd_reduce_masked(const bf16_t* dout, const bf16_t* y, const float* mean,
                          const float* invstd, const float* scale, const float* shift, long long M,
                          int C, float* part, hipStream_t st);

@@ -28,12 +28,9 @@ def _cpad(c):
     return max(8, (c + 7) // 8 * 8)
 
 
-# forward-style kernel configs (csrc/conv_igemm.hip igemm_fwd): 9-17 v3 igemm tiles
-# (tile = cfg % 3: 0 128x128, 1 128x64, 2 64x64; 12-13 32x32x16 MFMA, 15-17 two tiles of
-# register prefetch); 20/21/39/41/42 halo-staged unit-stride tiles (csrc/conv_halo.hip);
-# 60 the space-to-depth stem (csrc/conv_stem.hip); 90-93 pipelined LDS-DMA tiles
-# (csrc/conv_pipe.hip).  Measured on MI355X (tools/bench_conv.py ->
-# profiles/conv_kernels_r1.jsonl, conv_halo_tiles_b512_r1s4.jsonl):
+# What every kernel config id is and can do is one table, csrc/conv_cfg.h (read here through
+# _cfg); this module only decides which id a layer gets.  Measured on MI355X
+# (tools/bench_conv.py -> profiles/conv_kernels_r1.jsonl, conv_halo_tiles_b512_r1s4.jsonl):
 #   * strided taps, stride-2 dgrad parity classes below 256 channels, 1x1/s2 below 256
 #     channels: v3 tiles 15 / 13 / 11 by the block-count rule below (256-row tiles lose
 #     there: one workgroup per CU exposes the staging latency).
@@ -47,7 +44,26 @@ _STEM_CFG = 60
 # that remain.
 
 
-def dgrad_cfg(M, cin, k, stride, cout, H=0, W=0):
+_CFG_INFO = {}
+
+
+def _cfg(cfg, L=None, wgrad=False):
+    """The csrc/conv_cfg.h row of a forward-style (``wgrad``: weight-gradient) config id as a
+    dict, None for an id the table does not have; looked up once per id."""
+    key = (wgrad, cfg)
+    if key not in _CFG_INFO:
+        L = L or lib()
+        _CFG_INFO[key] = L.wgrad_cfg_info(cfg) if wgrad else L.conv_cfg_info(cfg)
+    return _CFG_INFO[key]
+
+
+def _can(cfg, what, L=None, wgrad=False):
+    """Capability ``what`` (a boolean field of the config's table row); False for an unknown id."""
+    info = _cfg(cfg, L, wgrad)
+    return bool(info and info[what])
+
+
+def dgrad_cfg(M, cin, k, stride, cout, W=0):
     """Kernel config of a data-gradient GEMM (dX has M pixels of ``cin`` channels)."""
     return pick_cfg(M, cin, k, stride, cout, W=W)
 
@@ -438,7 +454,7 @@ def convbn_fwd(layer, x, ctx, train, residual=None, raw=False, pre=None):
         # per step than the in-LDS transform that delayed every pipeline stage (and layer 2
         # measures the same either way, as does layer 1: profiles/pipe_pre_materialise_ab_r4q.txt,
         # profiles/layer12_pre_materialise_ab_r4u.txt)
-        if cfg in (39, 41, 42, 80):
+        if _can(cfg, "pre_bn", L):
             pre_kw = dict(pre_scale=pre[0], pre_shift=pre[1])
         else:  # not a halo-kernel shape: materialise the previous BN output
             x = _materialise(x, pre)
@@ -448,7 +464,7 @@ def convbn_fwd(layer, x, ctx, train, residual=None, raw=False, pre=None):
     shift = torch.empty(cout, **f32)
     use_batch = layer.training
     if use_batch:
-        T = L.conv_stats_rows(M, cfg, cout)
+        T = L.conv_stats_rows(M, cfg)
         stats = torch.empty(T * 2 * cout, **f32)
         L.conv_fwd(x, wf, y, stats, None, k, k, s, p, cfg, **pre_kw)
         mean = torch.empty(cout, **f32)
@@ -497,28 +513,20 @@ def convbn_fwd(layer, x, ctx, train, residual=None, raw=False, pre=None):
     return out
 
 
-# the v3 igemm tiles whose multi-geometry launch (a stride-2 data gradient's 4 parity classes)
-# takes the merged projection segment and the BN-backward reduction epilogue
-_MULTI_IGEMM = (11, 12, 13, 14, 15, 16, 17)
-# ... and the pipelined tiles (layer 4), whose merged segment needs the projection's channel
-# count equal to dy's (true of every ResNet projection)
-_MULTI_PIPE = (90, 91, 92, 93)
-
-
 def _dgrad_red(L, red_for, cfg, stride, dx, complete_s2=False):
     """conv_dgrad kwargs that reduce the consumer BN's backward sums in the dgrad epilogue
     (see convbn_bwd ``red_for``); {} when the kernel or the layer does not qualify.
 
-    cfg 80 (layer1), the pipelined tiles (90-93, layers 3-4) and the cfg 42 halo tile
-    (layer2) take a plain ReLU consumer (mask from y*scale + shift > 0), the residual
-    block's 1-bit mask, and the fused identity-skip add (the consumer's output gradient is
-    dgrad + skip).  The stem (BN + ReLU + max-pool) reduces over the pooled grid: y is its
+    The kernels with the epilogue (``red_s1`` in csrc/conv_cfg.h: layer1's resident-weight
+    kernel, the pipelined tiles of layers 3-4, layer2's halo tile) take a plain ReLU consumer
+    (mask from y*scale + shift > 0), the residual block's 1-bit mask, and the fused
+    identity-skip add (the consumer's output gradient is dgrad + skip).  The stem (BN + ReLU + max-pool) reduces over the pooled grid: y is its
     value at each window's argmax (ctx["yarg"]), as bn_bwd_reduce_masked does."""
     rl, rctx = red_for
     # stride 2: only a data gradient that writes dx complete in one launch (the projection's
     # 1x1/s2 segment merged in, ``complete_s2``) can reduce its consumer's sums
-    s2_ok = stride == 2 and complete_s2 and (cfg in _MULTI_IGEMM or cfg in _MULTI_PIPE)
-    kernel_ok = (stride == 1 and (cfg == 80 or 90 <= cfg <= 93 or cfg == 42)) or s2_ok
+    kernel_ok = (_can(cfg, "red_s1", L) if stride == 1
+                 else stride == 2 and complete_s2 and _can(cfg, "multi_merge_red", L))
     pool = getattr(rl, "pool_k", 0)
     y = rctx.get("yarg") if pool else rctx.get("y")
     if (not kernel_ok or not rl.relu or y is None
@@ -540,7 +548,7 @@ def _dgrad_red(L, red_for, cfg, stride, dx, complete_s2=False):
     # at ~2 TB/s; profiles/side_stream_sweep_r4f.txt)
     N, H, W, C = dx.shape
     rows = (L.dgrad_s2_red_rows(N, H, W, cfg) if stride == 2
-            else L.conv_stats_rows(N * H * W, cfg, C))
+            else L.conv_stats_rows(N * H * W, cfg))
     part = torch.empty(rows * 2 * C, device=dx.device, dtype=torch.float32)
     rctx["pre_sums"] = dict(pre_slab=part, pre_rows=rows)
     kw = dict(red_y=y, red_scale=rctx["scale"], red_shift=rctx["shift"],
@@ -562,7 +570,7 @@ def convbn_bwd(layer, dout, ctx, need_dx, dx_add=None, dx_into=None, fused_skip=
                   ("masked", dout, mask) for the consumer's dgrad epilogue (saves writing
                   and re-reading one activation-sized tensor per identity block)
     ``red_for``  : (layer, ctx) of the ConvBN + ReLU whose output gradient dx is.  When the
-                  dgrad kernel supports it (cfg 80), that BN's backward reduction (Σdz, Σdz·x̂)
+                  dgrad kernel supports it (_dgrad_red), that BN's backward reduction (Σdz, Σdz·x̂)
                   runs in this dgrad's epilogue and is left in its ctx["pre_sums"], so its
                   own backward skips the pass that re-reads dx and y
     ``phase``    : 0 = the whole backward; 1 = only the BatchNorm backward (dy kept in ctx),
@@ -675,7 +683,7 @@ def convbn_bwd(layer, dout, ctx, need_dx, dx_add=None, dx_into=None, fused_skip=
             pre_kw = {}
             xw = x
             if pre is not None:
-                if wcfg in (4, 5, 8):
+                if _can(wcfg, "pre_bn", L, wgrad=True):
                     pre_kw = dict(pre_scale=pre[0], pre_shift=pre[1])
                 else:
                     xw = _materialise(x, pre)
@@ -687,7 +695,7 @@ def convbn_bwd(layer, dout, ctx, need_dx, dx_add=None, dx_into=None, fused_skip=
     if need_dx and not ctx["first"]:
         _, wd = packed_weights(layer, need_wd=True)
         N_, H, W, Cin = x.shape
-        cfg = dgrad_cfg(N_ * H * W, Cin, k, s, cout, H, W)
+        cfg = dgrad_cfg(N_ * H * W, Cin, k, s, cout, W)
         if dx_into is not None:
             dx = dx_into
             L.conv_dgrad(dy, wd, dx_into, k, k, s, p, dx_into, cfg)
@@ -695,11 +703,11 @@ def convbn_bwd(layer, dout, ctx, need_dx, dx_add=None, dx_into=None, fused_skip=
             dx = empty_nhwc(N_, H, W, Cin, x)
             merge_kw = {}
             if (shortcut is not None and s == 2 and k == 3 and p == 1 and dx_add is None
-                    and (cfg in _MULTI_IGEMM or cfg in _MULTI_PIPE)
+                    and _can(cfg, "multi_merge_red", L)
                     and H % 2 == 0 and W % 2 == 0):
                 dy2, wd2 = shortcut["join"]()
                 if (dy2.shape[:3] == dy.shape[:3] and dy2.shape[3] % 64 == 0
-                        and (cfg in _MULTI_IGEMM or dy2.shape[3] == dy.shape[3])):
+                        and (not _can(cfg, "merge_same_c", L) or dy2.shape[3] == dy.shape[3])):
                     merge_kw = dict(dy2=dy2, wd2=wd2)
                     shortcut["merged"] = True
             red_kw = (_dgrad_red(L, red_for, cfg, s, dx, complete_s2=bool(merge_kw))

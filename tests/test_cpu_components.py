@@ -330,11 +330,11 @@ def test_res64_picked_for_layer1():
     128-pixel halo fits the kernel's 256-row LDS image."""
     from dmlab.ops.convbn import pick_cfg, dgrad_cfg
     assert pick_cfg(1024 * 56 * 56, 64, 3, 1, 64, W=56) == 80
-    assert dgrad_cfg(1024 * 56 * 56, 64, 3, 1, 64, 56, 56) == 80
+    assert dgrad_cfg(1024 * 56 * 56, 64, 3, 1, 64, 56) == 80
     assert pick_cfg(1024 * 56 * 56, 64, 3, 1, 64) != 80        # width unknown
     assert pick_cfg(4 * 112 * 112, 64, 3, 1, 64, W=112) != 80  # halo too wide
     assert pick_cfg(1024 * 28 * 28, 128, 3, 1, 128, W=28) != 80
-    assert dgrad_cfg(1024 * 56 * 56, 64, 3, 2, 128, 56, 56) != 80  # layer2 c1 data gradient
+    assert dgrad_cfg(1024 * 56 * 56, 64, 3, 2, 128, 56) != 80  # layer2 c1 data gradient
 
 
 def test_wgrad_res64_plan():
@@ -372,7 +372,11 @@ def test_dgrad_red_selection():
     import torch
     from dmlab.ops import convbn as CB
 
-    L = NS(conv_stats_rows=lambda M, cfg, C: 7)
+    import cfg_table
+
+    fwd, _ = cfg_table.records()  # the real table, as tests/native/cfg_table.cpp prints it
+    CB._CFG_INFO.clear()
+    L = NS(conv_stats_rows=lambda M, cfg: 7, conv_cfg_info=fwd.get)
     dx = torch.zeros(2, 4, 4, 64)
 
     def ctx(has_res=False, mask=False, pool=False):
@@ -404,3 +408,74 @@ def test_dgrad_red_selection():
     assert CB._dgrad_red(L, (stem, c), 80, 1, dx)["red_y"] is c["yarg"]
     c = ctx(has_res=True, mask=True)
     assert CB._dgrad_red(L, (relu, c), 80, 1, dx)["red_mask"] is c["mask"]
+    CB._CFG_INFO.clear()
+
+
+def test_cfg_table_reproduces_kernel_capabilities():
+    """csrc/conv_cfg.h answers, for every id, what the launchers, the bindings and convbn.py
+    each used to restate by hand (the values written out here are those rules)."""
+    import cfg_table
+
+    fwd, wgrad = cfg_table.records()
+    assert sorted(fwd) == [9, 10, 11, 12, 13, 14, 15, 16, 17, 39, 41, 42, 60, 80, 90, 91, 92, 93]
+    assert sorted(wgrad) == [2, 3, 4, 5, 6, 7, 8]
+    family = {"igemm": range(9, 18), "halo": (39, 41, 42), "stem": (60,), "res64": (80,),
+              "pipe": range(90, 94)}
+    assert {i: r["family"] for i, r in fwd.items()} == {i: f for f, ids in family.items() for i in ids}
+    # statistics row tiles (80: one row per workgroup of the persistent kernel)
+    rowtile = {9: 128, 10: 128, 11: 64, 12: 128, 13: 128, 14: 64, 15: 128, 16: 128, 17: 64,
+               39: 256, 41: 256, 42: 128, 60: 256, 80: 0, 90: 256, 91: 256, 92: 256, 93: 256}
+    assert {i: r["rowtile"] for i, r in fwd.items()} == rowtile
+    # igemm tiles: 9-11 / 12-14 / 15-17 = 128x128, 128x64, 64x64; 14 is an alias of 11
+    tile = lambda r: (r["bm"], r["bn"], r["wm"], r["wn"], r["mf32"], r["depth"])
+    assert [tile(fwd[i]) for i in range(9, 18)] == [
+        (128, 128, 2, 2, 0, 1), (128, 64, 2, 2, 0, 1), (64, 64, 2, 2, 0, 1),
+        (128, 128, 2, 2, 1, 1), (128, 64, 2, 2, 1, 1), (64, 64, 2, 2, 0, 1),
+        (128, 128, 2, 2, 1, 2), (128, 64, 2, 2, 1, 2), (64, 64, 2, 2, 0, 2)]
+    assert {k: v for k, v in fwd[14].items() if k != "id"} == {k: v for k, v in fwd[11].items() if k != "id"}
+    # pipelined tiles: BN, waves, workgroups per CU; halo tiles: BN and conv_halo's selector
+    assert [(fwd[i]["bn"], fwd[i]["wm"], fwd[i]["wn"], fwd[i]["minw"]) for i in range(90, 94)] == [
+        (256, 2, 4, 1), (128, 4, 2, 1), (128, 2, 2, 1), (64, 4, 1, 2)]
+    assert {i: (fwd[i]["bn"], fwd[i]["halo_waves"]) for i in (39, 41, 42)} == {
+        39: (64, 16), 41: (64, 32), 42: (128, 4 | 0x100)}
+    ids = lambda table, key: {i for i, r in table.items() if r[key]}
+    assert ids(fwd, "pre_bn") == {39, 41, 42, 80}
+    assert ids(wgrad, "pre_bn") == {4, 5, 8}
+    assert ids(fwd, "red_s1") == {42, 80, 90, 91, 92, 93}
+    multi = {11, 12, 13, 14, 15, 16, 17, 90, 91, 92, 93}
+    assert ids(fwd, "multi") == multi and ids(fwd, "multi_merge_red") == multi
+    assert ids(fwd, "merge_same_c") == {90, 91, 92, 93}
+    assert {i: r["pre_reroute"] for i, r in fwd.items() if r["pre_reroute"]} == dict.fromkeys(range(90, 94), 41)
+    # fallbacks: 42 -> tile 12; 39 / 41 / 60 -> 256x64 (-1); 90-93 -> 256x128 (-2) when
+    # Ncols % 128 == 0, else 256x64; igemm runs everything and 80 throws (0)
+    fb = {i: (r["fallback"], r["fallback128"]) for i, r in fwd.items() if r["fallback"] or r["fallback128"]}
+    assert fb == {39: (-1, -1), 41: (-1, -1), 42: (12, 12), 60: (-1, -1), 90: (-1, -2), 91: (-1, -2),
+                  92: (-1, -2), 93: (-1, -2)}
+    # weight gradient: v2 tiles, taps per block, 7 / 4 / 5 -> 3, or 2 when Ncols % 128 == 0
+    assert {i: (r["family"], r["bm"], r["bk"], r["taps"], r["fallback"], r["fallback128"])
+            for i, r in wgrad.items()} == {
+        2: ("v2", 128, 128, 0, 0, 0), 3: ("v2", 64, 128, 0, 0, 0), 4: ("halo", 0, 0, 9, 3, 2),
+        5: ("halo", 0, 0, 3, 3, 2), 6: ("v2", 64, 256, 0, 0, 0), 7: ("s2", 0, 0, 9, 3, 2),
+        8: ("res64", 0, 0, 0, 0, 0)}
+
+
+def test_cfg_outside_table_is_none():
+    """An id the table does not have yields None: the fallback-only tiles (negative ids), the
+    removed tiles, the other table's ids; convbn's cached lookup then answers False."""
+    import cfg_table
+    from types import SimpleNamespace as NS
+    from dmlab.ops import convbn as CB
+
+    fwd, wgrad = cfg_table.records()
+    for i in (-2, -1, 0, 2, 8, 18, 20, 21, 43, 94):
+        assert fwd.get(i) is None, i
+    for i in (-1, 0, 1, 9, 80):
+        assert wgrad.get(i) is None, i
+    CB._CFG_INFO.clear()
+    calls = []
+    L = NS(conv_cfg_info=lambda i: calls.append(i) or fwd.get(i), wgrad_cfg_info=wgrad.get)
+    assert CB._cfg(20, L) is None and not CB._can(20, "pre_bn", L)
+    assert CB._can(42, "red_s1", L) and CB._can(42, "pre_bn", L) and not CB._can(42, "multi", L)
+    assert CB._can(8, "pre_bn", L, wgrad=True) and not CB._can(8, "pre_bn", L)
+    assert calls == [20, 42, 8]  # one lookup per id, the answer cached
+    CB._CFG_INFO.clear()

@@ -22,6 +22,19 @@ def test_geom_fastdiv_asan_ubsan(tmp_path):
     assert r.stdout.startswith("ok"), r.stdout
 
 
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
+def test_cfg_table_asan_ubsan(tmp_path):
+    """The conv kernel config tables (csrc/conv_cfg.h): the stand-alone consistency check
+    under AddressSanitizer + UBSan."""
+    exe = tmp_path / "cfg_table"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+           "-fno-sanitize-recover=all", str(HERE / "native" / "cfg_table.cpp"), "-o", str(exe)]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.splitlines()[-1] == "ok", r.stdout
+
+
 ROOT = HERE.parent
 
 

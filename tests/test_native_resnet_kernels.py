@@ -799,3 +799,26 @@ def test_wgrad_reduce_vector_matches_scalar(dev, S):
         out.append(d)
     assert torch.equal(out[0], out[1])
     assert _rel(out[0], ref) < 2e-3
+
+
+def test_cfg_info_matches_native_table():
+    """The extension's conv_cfg_info / wgrad_cfg_info return, for every id, the record that the
+    stand-alone program prints from csrc/conv_cfg.h (None outside the table), and
+    conv_stats_rows is ceil(M / row tile) for the tile families.  Launches no kernel."""
+    import cfg_table
+
+    fwd, wgrad = cfg_table.records()
+    L = lib()
+    for i, rec in fwd.items():
+        assert L.conv_cfg_info(i) == rec, i
+        bm = rec["rowtile"]
+        if rec["family"] != "res64":
+            assert bm == rec["bm"] > 0
+            for M in (1, bm, bm + 1):
+                assert L.conv_stats_rows(M, i) == -(-M // bm), (i, M)
+    for i, rec in wgrad.items():
+        assert L.wgrad_cfg_info(i) == rec, i
+    for i in (-1, 0, 18, 43, 94):
+        assert L.conv_cfg_info(i) is None
+    for i in (0, 1, 9):
+        assert L.wgrad_cfg_info(i) is None

@@ -91,7 +91,7 @@ def main():
                 if cfg == 80 and (C, Co, k, s) != (64, 64, 3, 1):
                     continue
                 M = N * OH * OH
-                T = L.conv_stats_rows(M, cfg, Co)
+                T = L.conv_stats_rows(M, cfg)
                 st = torch.empty(T * 2 * Co, device=dev)
                 t = timeit(lambda: L.conv_fwd(x, wf, y, st, None, k, k, s, p, cfg), a.iters)
                 row[f"fwd_c{cfg}_TF"] = round(flops / t / 1e12, 1)

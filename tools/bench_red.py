@@ -58,7 +58,7 @@ def main():
         mu = torch.randn(C, device=dev, generator=g) * 0.2
         inv = torch.rand(C, device=dev, generator=g) + 0.5
         mask = torch.randint(0, 256, (N * H * H * C // 8,), device=dev, dtype=torch.uint8)
-        rows = L.conv_stats_rows(N * H * H, cfg, C)
+        rows = L.conv_stats_rows(N * H * H, cfg)
         part = torch.empty(rows * 2 * C, device=dev)
         red = dict(red_y=yb, red_scale=sc, red_shift=sh, red_mean=mu, red_invstd=inv, red_part=part)
         fns = {

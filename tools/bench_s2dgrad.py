@@ -65,7 +65,7 @@ def main():
         cfgs = [int(c) for c in a.cfgs.split(",") if Cin % WIDTH.get(int(c), 64) == 0]
         fns = {}
         if a.variants:  # the default tile alone: plain / + merged projection / + reduction
-            cfg = dgrad_cfg(N * H * H, Cin, 3, 2, Cout, H, H)
+            cfg = dgrad_cfg(N * H * H, Cin, 3, 2, Cout, H)
             rows = L.dgrad_s2_red_rows(N, H, H, cfg)
             part = torch.empty(rows * 2 * Cin, device=dev)
             red = dict(red_y=yb, red_scale=vec[0], red_shift=vec[1], red_mean=vec[2],
@@ -98,10 +98,10 @@ def main():
         flops = 2.0 * N * OH * OH * Cout * Cin * 10  # 9 taps + the 1x1
         res = {c: round(min(v), 1) for c, v in t.items()}
         if a.variants:
-            print(json.dumps({"shape": name, "cfg": dgrad_cfg(N * H * H, Cin, 3, 2, Cout, H, H),
+            print(json.dumps({"shape": name, "cfg": dgrad_cfg(N * H * H, Cin, 3, 2, Cout, H),
                               "us": res}), flush=True)
             continue
-        print(json.dumps({"shape": name, "default_cfg": dgrad_cfg(N * H * H, Cin, 3, 2, Cout, H, H),
+        print(json.dumps({"shape": name, "default_cfg": dgrad_cfg(N * H * H, Cin, 3, 2, Cout, H),
                           "us": res, "tflops": {c: round(flops / v / 1e6, 1) for c, v in res.items()}}),
               flush=True)
 
