@@ -85,6 +85,49 @@ void rows_mean(at::Tensor x, at::Tensor out, double scale) {
                 (float)scale, cur_stream());
 }
 
+// ------------------------------------------------------------------ q8 codec (csrc/gradq.hip)
+void q8_encode(at::Tensor g, c10::optional<at::Tensor> r, at::Tensor payload,
+               int64_t max_blocks) {
+  CHECK_CUDA(g); CHECK_F32(g); CHECK_CONTIG(g);
+  CHECK_CUDA(payload); CHECK_CONTIG(payload);
+  TORCH_CHECK(payload.scalar_type() == at::kByte, "payload must be uint8");
+  TORCH_CHECK(g.dim() == 1 && payload.dim() == 1, "g and payload must be 1-d");
+  TORCH_CHECK(payload.numel() == dm::q8_payload_bytes(g.numel()),
+              "payload must hold q8_payload_bytes(n) = ", dm::q8_payload_bytes(g.numel()),
+              " bytes, got ", payload.numel());
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(payload.data_ptr()) & 3) == 0,
+              "payload must be 4-B aligned");
+  TORCH_CHECK(g.device() == payload.device(), "g and payload on different devices");
+  float* rp = nullptr;
+  if (r.has_value() && r->defined()) {
+    CHECK_CUDA(*r); CHECK_F32(*r); CHECK_CONTIG(*r);
+    TORCH_CHECK(r->dim() == 1 && r->numel() == g.numel(), "residual size mismatch");
+    TORCH_CHECK(r->device() == g.device(), "g and residual on different devices");
+    rp = r->data_ptr<float>();
+  }
+  const DeviceGuard guard(g.device());
+  dm::q8_encode(g.data_ptr<float>(), rp, payload.data_ptr<uint8_t>(), g.numel(),
+                (int)max_blocks, cur_stream());
+}
+
+void q8_decode_mean(at::Tensor gathered, at::Tensor out, double scale, int64_t max_blocks) {
+  CHECK_CUDA(gathered); CHECK_CONTIG(gathered);
+  CHECK_CUDA(out); CHECK_F32(out); CHECK_CONTIG(out);
+  TORCH_CHECK(gathered.scalar_type() == at::kByte, "gathered must be uint8");
+  TORCH_CHECK(gathered.dim() == 2 && out.dim() == 1, "gathered must be [ws, payload], out 1-d");
+  TORCH_CHECK(gathered.size(0) >= 1 && gathered.size(0) <= INT32_MAX, "bad row count");
+  TORCH_CHECK(gathered.size(1) == dm::q8_payload_bytes(out.numel()),
+              "rows must hold q8_payload_bytes(n) = ", dm::q8_payload_bytes(out.numel()),
+              " bytes, got ", gathered.size(1));
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(gathered.data_ptr()) & 3) == 0,
+              "gathered must be 4-B aligned");
+  TORCH_CHECK(gathered.device() == out.device(), "gathered and out on different devices");
+  const DeviceGuard guard(out.device());
+  dm::q8_decode_mean(gathered.data_ptr<uint8_t>(), gathered.size(1), (int)gathered.size(0),
+                     out.data_ptr<float>(), out.numel(), (float)scale, (int)max_blocks,
+                     cur_stream());
+}
+
 // ------------------------------------------------------------------ LARS (csrc/lars.hip)
 // Build the segment and chunk tables for tensors at `offsets` (elements, 16-B aligned) with
 // `numels` elements each inside a flat buffer of `total` elements.  Returns CPU int64 tensors
@@ -595,6 +638,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_step", &adam_step, "fused flat Adam step");
   m.def("cast_f32_bf16", &cast_f32_bf16, "fp32 -> bf16 cast");
   m.def("rows_mean", &rows_mean, "[rows,N] -> [N] scaled row sum");
+  m.def("q8_payload_bytes", [](int64_t n) { return (int64_t)dm::q8_payload_bytes(n); },
+        "bytes of one rank's q8 payload for n gradient elements");
+  m.def("q8_encode", &q8_encode, "fp32 slice (+ residual) -> q8 payload (scales, int8 codes)",
+        py::arg("g"), py::arg("r"), py::arg("payload"), py::arg("max_blocks") = 0);
+  m.def("q8_decode_mean", &q8_decode_mean, "[ws, payload] -> scale * sum of decoded rows",
+        py::arg("gathered"), py::arg("out"), py::arg("scale"), py::arg("max_blocks") = 0);
   m.def("lars_chunk", &dm::lars_chunk, "elements per LARS chunk (compile-time constant)");
   m.def("lars_table", &lars_table, "host-validated LARS segment/chunk tables (CPU int64)",
         py::arg("offsets"), py::arg("numels"), py::arg("adapted"), py::arg("total"));

@@ -18,6 +18,16 @@ void cast_f32_bf16(const float* x, bf16_t* y, long long n, hipStream_t st);
 void rows_mean(const float* x, float* out, int rows, long long n, float scale,
                hipStream_t st);
 
+// gradq.hip: "q8" block-wise int8 gradient codec (blocks of 256 from the slice's start).
+// payload = ceil(n/256) fp32 scales, n int8 codes, padding to 16 bytes (q8_payload_bytes);
+// r = nullptr: no error feedback.  gathered holds ws payloads row_bytes apart;
+// out = scale * sum over rows of code*scale in row order.  max_blocks > 0 caps the grid.
+long long q8_payload_bytes(long long n);
+void q8_encode(const float* g, float* r, uint8_t* payload, long long n, int max_blocks,
+               hipStream_t st);
+void q8_decode_mean(const uint8_t* gathered, long long row_bytes, int ws, float* out,
+                    long long n, float scale, int max_blocks, hipStream_t st);
+
 // lars.hip: fused LARS step over the flat buffers (3 launches).  seg [n_tensors,5] and
 // chunks [n_chunks,3] are the int64 device tables described there; hyper holds
 // lars_hyper_count() floats (lr, momentum, weight decay, trust coefficient, eps,

@@ -234,8 +234,12 @@ class GradAggregator:
 
     ``method``: ``allreduce`` | ``allgather`` | ``allgather_ref`` (B1 compat) |
     ``allreduce_xgmi`` (the one-shot peer-memory kernel of :mod:`dmlab.parallel.xgmi` over
-    the flat gradient buffer, averaging folded into its epilogue: GPU ranks of one node);
+    the flat gradient buffer, averaging folded into its epilogue: GPU ranks of one node) |
+    ``allgather_q8`` (block-wise int8 quantisation with error feedback,
+    :mod:`dmlab.parallel.compress`: one encode, one all-gather of the ``uint8`` payload, one
+    decode-mean; ``error_feedback=False`` drops the residual; flat granularity only);
     ``granularity``: ``flat`` (one coalesced collective) | ``per_param``.
+    ``bytes_per_call``: the bytes this rank hands to the collectives per aggregation.
 
     ``timing``:
       * ``"events"`` (default on a HIP device): a pair of HIP events on the current stream
@@ -250,8 +254,13 @@ class GradAggregator:
     On the CPU (gloo) the collectives are synchronous and wall time is exact."""
 
     def __init__(self, model, method="allreduce", granularity="flat", timing=None,
-                 sync_timing=None, force=False):
+                 sync_timing=None, force=False, error_feedback=True):
         self.model, self.method, self.granularity = model, method, granularity
+        if method == "allgather_q8" and granularity != "flat":
+            raise ValueError("allgather_q8 quantises blocks of the flat gradient buffer: "
+                             "granularity must be 'flat', not %r" % (granularity,))
+        self.error_feedback = bool(error_feedback)
+        self._q8 = None  # (compressor, payload, gathered), built at the first aggregation
         if timing is None:
             # the legacy flag keeps its meaning: True = synchronised wall clock, False = host
             # wall time only; neither given = device-side event timing
@@ -284,8 +293,61 @@ class GradAggregator:
 
                 self._xgmi = XGMIAllReduce(cap=flat.grad.numel())
             self._xgmi(flat.grad, scale=1.0 / ws)
+        elif self.method == "allgather_q8":
+            self._aggregate_q8()
         else:
             raise ValueError(self.method)
+
+    @torch.no_grad()
+    def _aggregate_q8(self):
+        ws = env.get_world_size()
+        if ws <= 1 and not (self.force and env.is_initialized()):
+            return
+        flat = _flat_of_model(self.model)
+        gs = None
+        if flat is not None and flat.attached():
+            buf = flat.grad
+        else:
+            gs = _grads(self.model)
+            if not gs:
+                return
+            buf = _flatten(gs)
+        if self._q8 is None:
+            from .compress import Q8Compressor, payload_bytes
+
+            nbytes = payload_bytes(buf.numel())
+            self._q8 = (Q8Compressor(buf.numel(), buf.device, self.error_feedback),
+                        torch.zeros(nbytes, dtype=torch.uint8, device=buf.device),
+                        torch.zeros((ws, nbytes), dtype=torch.uint8, device=buf.device))
+        comp, payload, gathered = self._q8
+        comp.encode(buf, 0, payload)
+        _all_gather_rows(gathered, payload)
+        comp.decode_mean(gathered, buf, 1.0 / ws)
+        if gs is not None:
+            _unflatten_into(buf, gs)
+
+    @property
+    def compressor(self):
+        """The q8 codec state (residual) once the first aggregation has built it."""
+        return self._q8[0] if self._q8 is not None else None
+
+    @property
+    def bytes_per_call(self) -> int:
+        """Bytes this rank hands to the collectives per aggregation: the flat gradient buffer
+        (alignment padding included) for the coalesced methods, the parameters' own elements
+        for the per-tensor ones, the q8 payload for ``allgather_q8``."""
+        flat = _flat_of_model(self.model)
+        per_tensor = self.granularity == "per_param" or self.method == "allgather_ref"
+        if flat is not None and not per_tensor:
+            n, el = flat.grad.numel(), flat.grad.element_size()
+        else:
+            ps = [p for p in self.model.parameters() if p.requires_grad]
+            n, el = sum(p.numel() for p in ps), (ps[0].element_size() if ps else 4)
+        if self.method == "allgather_q8":
+            from .compress import payload_bytes
+
+            return payload_bytes(n)
+        return n * el
 
     def __call__(self):
         """Aggregate; returns the host-measured seconds, or None with event timing."""

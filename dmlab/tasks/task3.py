@@ -88,6 +88,11 @@ def parse_args(argv=None):
                         "world size > 1 on GPUs a startup self-check runs one xGMI call against "
                         "RCCL (exact); auto/xgmi use the kernel for LeNet only if it passes on "
                         "every rank (RCCL otherwise); ResNet-18 stays on RCCL under auto")
+    p.add_argument("--compress", default="none", choices=["none", "q8"],
+                   help="q8: DDP exchanges block-wise int8 gradients with error feedback "
+                        "(all-gather + decode-mean) instead of all-reducing fp32")
+    p.add_argument("--no-error-feedback", action="store_true",
+                   help="--compress q8: do not carry the quantisation error to the next step")
     p.add_argument("--data", default="./data")
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--train-samples", type=int, default=None)
@@ -125,6 +130,12 @@ def main(argv=None):
                          "step; --label-smoothing needs the layer-wise loop (--fused auto or 0)")
     if a.topk < 0:
         raise SystemExit("--topk must be >= 0")
+    if a.compress != "none" and a.dp != "ddp":
+        raise SystemExit("--compress q8 runs inside DDP's buckets: it needs --dp ddp")
+    if a.compress != "none" and a.allreduce == "xgmi":
+        raise SystemExit("--compress q8 all-gathers its payload: not with --allreduce xgmi")
+    if a.no_error_feedback and a.compress == "none":
+        raise SystemExit("--no-error-feedback belongs to --compress q8")
     if a.fused == "1" and a.augment != "none":
         raise SystemExit("--fused 1 reads the dataset rows inside the fused LeNet step; "
                          "--augment needs the layer-wise loop (--fused auto or 0)")
@@ -145,6 +156,8 @@ def main(argv=None):
                    device_type=a.device)
     rank, ws = env.get_rank(), env.get_world_size()
     checks = {}
+    if a.compress != "none" and a.allreduce == "auto":
+        a.allreduce = "rccl"  # compressed buckets go through the group's all-gather
     if ws > 1:
         # the device paths this run depends on, proven before training (selfcheck module)
         from dmlab.parallel import selfcheck
@@ -198,14 +211,22 @@ def main(argv=None):
     else:
         opt = SGD(model.parameters(), lr=a.lr, momentum=a.momentum,
                   weight_decay=a.weight_decay)
+    resumed = {}
     if a.resume:
         from dmlab.utils import checkpoint
 
-        checkpoint.load(a.resume, model, opt)
+        resumed = checkpoint.load(a.resume, model, opt)
     if a.dp == "ddp":
         net = DDP(model, bucket_cap_mb=a.bucket_mb,  # broadcasts rank-0 params
-                  small_allreduce="xgmi" if a.allreduce == "xgmi" and dev.type == "cuda" else None)
+                  small_allreduce="xgmi" if a.allreduce == "xgmi" and dev.type == "cuda" else None,
+                  compress=None if a.compress == "none" else a.compress,
+                  error_feedback=not a.no_error_feedback)
         net.fold_average_into(opt)
+        if resumed.get("q8_residual") is not None and net.compressor is not None:
+            # the residual is per-rank training state; it only fits the same world size
+            if not net.load_residual_state(resumed["q8_residual"]) and rank == 0:
+                print("checkpoint: q8 residual not restored (world size, buffer size or "
+                      "--no-error-feedback differs); starting from a zero residual")
         agg = None
     else:
         comm.init_parameters(model)
@@ -254,7 +275,10 @@ def main(argv=None):
     if a.save:
         from dmlab.utils import checkpoint
 
-        checkpoint.save(a.save, model, opt, epochs=a.epochs)
+        extra = {}
+        if a.compress != "none":  # every rank's residual (a collective), kept by rank 0
+            extra["q8_residual"] = net.residual_state()
+        checkpoint.save(a.save, model, opt, epochs=a.epochs, **extra)
     sharded = a.eval == "sharded"
     ev_kw = {}
     if a.augment == "rrc":  # evaluate on the deterministic centre crop of the same size
@@ -269,7 +293,9 @@ def main(argv=None):
     elif not a.no_test and a.topk == 0 and rank == 0:
         stats["accuracy"] = test(model, DeviceLoader(test_set.to(dev, dtype=act), 32, **ev_kw))
     stats.update(checks)
-    stats.update(rank=rank, world_size=ws, sampler=a.sampler, dp=a.dp,
+    stats.update(rank=rank, world_size=ws, sampler=a.sampler, dp=a.dp, compress=a.compress,
+                 comm_bytes_per_step=(net.comm_bytes_per_step if a.dp == "ddp"
+                                      else agg.bytes_per_call),
                  samples_per_s=stats["samples"] * ws / stats["train_time"])
     if a.json and rank == 0:
         with open(a.json, "w") as f:
