@@ -462,6 +462,54 @@ void bn_stats_finalize(at::Tensor stats, int64_t T, double count, at::Tensor gam
                         cur_stream());
 }
 
+// ---- cross-rank (synchronized) BatchNorm: float64 rows / sums, the global count on the device
+static double* need_f64(const at::Tensor& t, const char* name, int64_t n) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kDouble && t.is_contiguous() && t.numel() == n,
+              name, ": contiguous float64 device tensor of ", n, " elements");
+  return t.data_ptr<double>();
+}
+
+// stats [T][2C], this rank's element count -> row [mean (C) | M2 (C) | n] float64
+void bn_sync_local(at::Tensor stats, int64_t T, double count, int64_t C, at::Tensor row,
+                   at::Tensor work) {
+  TORCH_CHECK(C >= 1 && T >= 1 && count >= 1, "bn_sync_local: C, T, count >= 1");
+  need_f32(stats, "stats", T * 2 * C);
+  need_f32(work, "work", 256 * 2 * C);
+  double* rp = need_f64(row, "row", 2 * C + 1);
+  TORCH_CHECK(row.device() == stats.device() && work.device() == stats.device());
+  const DeviceGuard guard(stats.device());
+  dm::bn_sync_local(fp(stats), (int)T, (int)C, count, rp, fp(work), cur_stream());
+}
+
+// rows [ws][2C+1] (every rank's bn_sync_local row, rank order) -> scale/shift/mean/invstd, the
+// running statistics, num_batches += 1, total = Σ n (float64 device scalar)
+void bn_sync_finalize(at::Tensor rows, at::Tensor gamma, at::Tensor beta,
+                      c10::optional<at::Tensor> rmean, c10::optional<at::Tensor> rvar,
+                      double momentum, double eps, at::Tensor scale, at::Tensor shift,
+                      at::Tensor mean, at::Tensor invstd, c10::optional<at::Tensor> num_batches,
+                      at::Tensor total) {
+  const int C = gamma.numel();
+  TORCH_CHECK(rows.dim() == 2 && rows.size(0) >= 1 && rows.size(1) == 2 * C + 1,
+              "rows: [ws][2C+1]");
+  const double* rp = need_f64(rows, "rows", rows.size(0) * (2 * C + 1));
+  double* tp = need_f64(total, "total", 1);
+  long long* nb = nullptr;
+  if (num_batches.has_value()) {
+    TORCH_CHECK(num_batches->scalar_type() == at::kLong && num_batches->numel() == 1 &&
+                num_batches->device() == rows.device(), "num_batches: int64 scalar on the device");
+    nb = (long long*)num_batches->data_ptr();
+  }
+  for (auto* t : {&gamma, &beta, &scale, &shift, &mean, &invstd}) need_f32(*t, "bn vec", C);
+  if (rmean.has_value()) need_f32(*rmean, "rmean", C);
+  if (rvar.has_value()) need_f32(*rvar, "rvar", C);
+  TORCH_CHECK(rmean.has_value() == rvar.has_value(), "running mean and var: both or neither");
+  const DeviceGuard guard(rows.device());
+  dm::bn_sync_finalize(rp, (int)rows.size(0), C, fp(gamma), fp(beta),
+                       rmean.has_value() ? fp(*rmean) : nullptr,
+                       rvar.has_value() ? fp(*rvar) : nullptr, momentum, eps, fp(scale), fp(shift),
+                       fp(mean), fp(invstd), nb, tp, cur_stream());
+}
+
 void bn_eval_coeffs(at::Tensor gamma, at::Tensor beta, at::Tensor rmean, at::Tensor rvar, double eps,
                     at::Tensor scale, at::Tensor shift) {
   const int C = gamma.numel();
@@ -551,7 +599,21 @@ void bn_backward(c10::optional<at::Tensor> dout, c10::optional<at::Tensor> out, 
                  c10::optional<at::Tensor> pidx, int64_t K, int64_t S, int64_t P,
                  at::Tensor dy, c10::optional<at::Tensor> dres, at::Tensor work,
                  c10::optional<at::Tensor> pre_slab, int64_t pre_rows,
-                 c10::optional<at::Tensor> mask) {
+                 c10::optional<at::Tensor> mask, int64_t stage,
+                 c10::optional<at::Tensor> sums, c10::optional<at::Tensor> total) {
+  // stage 1 / 2: the two halves of a cross-rank BatchNorm backward (see dm::bn_backward);
+  // sums [2C] float64 is written by stage 1 and read, summed over the ranks, by stage 2
+  TORCH_CHECK(stage >= 0 && stage <= 2, "stage: 0 whole, 1 sums, 2 apply");
+  double* sums_p = nullptr;
+  const double* total_p = nullptr;
+  if (stage != 0) {
+    TORCH_CHECK(sums.has_value(), "stage 1 / 2 need sums");
+    sums_p = need_f64(*sums, "sums", 2 * y.size(3));
+  }
+  if (stage == 2) {
+    TORCH_CHECK(total.has_value(), "stage 2 needs total");
+    total_p = need_f64(*total, "total", 1);
+  }
   need_bf16_nhwc(y, "y");
   need_bf16_nhwc(dy, "dy");
   TORCH_CHECK(dy.sizes() == y.sizes());
@@ -612,7 +674,24 @@ void bn_backward(c10::optional<at::Tensor> dout, c10::optional<at::Tensor> out, 
   dm::bn_backward(doutp, outp, bp(y), fp(mean), fp(invstd), fp(gamma), fp(dgamma), fp(dbeta),
                   (float)gbeta, M, C, (int)mode, scp, shp, pdyp, pidxp, y.size(1), y.size(2), OH,
                   OW, K, S, P, bp(dy), drp, fp(work), cur_stream(), pre_slab.has_value() ? fp(*pre_slab) : nullptr,
-                  (int)pre_rows, mp);
+                  (int)pre_rows, mp, (int)stage, sums_p, total_p);
+}
+
+// Stage "sums" of a coefficient-only BatchNorm backward (the fused stem): dgamma / dbeta from
+// this rank's pre-reduced partial rows, sums [2C] float64 out
+void bn_bwd_sums(at::Tensor pre_slab, int64_t pre_rows, int64_t C, at::Tensor dgamma,
+                 at::Tensor dbeta, double gbeta, at::Tensor work, at::Tensor sums) {
+  TORCH_CHECK(pre_rows >= 1 && C >= 1, "bn_bwd_sums: >= 1 row");
+  need_f32(pre_slab, "pre_slab", pre_rows * 2 * C);
+  need_f32(dgamma, "dgamma", C);
+  need_f32(dbeta, "dbeta", C);
+  need_f32(work, "work", 3 * C + 256 * 2 * C);
+  double* sp = need_f64(sums, "sums", 2 * C);
+  const DeviceGuard guard(pre_slab.device());
+  dm::bn_backward(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, fp(dgamma), fp(dbeta),
+                  (float)gbeta, 0, (int)C, 3, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 3, 2,
+                  1, nullptr, nullptr, fp(work), cur_stream(), fp(pre_slab), (int)pre_rows, nullptr,
+                  1, sp, nullptr);
 }
 
 void bn_relu_maxpool(at::Tensor y, at::Tensor scale, at::Tensor shift, at::Tensor out,
@@ -802,7 +881,11 @@ void stem_bwd_fused2(at::Tensor img, c10::optional<at::Tensor> idx, std::vector<
                      std::vector<double> nbi, at::Tensor wk, at::Tensor pdy, at::Tensor code4,
                      at::Tensor mean, at::Tensor invstd, at::Tensor gamma, at::Tensor dgamma,
                      at::Tensor dbeta, double gbeta, at::Tensor pre_slab, int64_t pre_rows,
-                     at::Tensor dw, double wbeta, at::Tensor work, at::Tensor dslab, int64_t grid) {
+                     at::Tensor dw, double wbeta, at::Tensor work, at::Tensor dslab, int64_t grid,
+                     c10::optional<at::Tensor> bn_sums, c10::optional<at::Tensor> bn_total) {
+  // bn_sums + bn_total (cross-rank BatchNorm): the coefficients come from the global sums (stage
+  // "apply" of dm::bn_backward); dgamma / dbeta were written by bn_bwd_sums and stay untouched
+  TORCH_CHECK(bn_sums.has_value() == bn_total.has_value(), "sums and total: both or neither");
   const ImgView v = img_view(img);
   TORCH_CHECK(dm::stem_fused_supported(v.H, v.W), "fused stem: unsupported input size");
   need_bf16_nhwc(pdy, "pdy");
@@ -826,7 +909,9 @@ void stem_bwd_fused2(at::Tensor img, c10::optional<at::Tensor> idx, std::vector<
   dm::bn_backward(nullptr, nullptr, nullptr, fp(mean), fp(invstd), fp(gamma), fp(dgamma), fp(dbeta),
                   (float)gbeta, M, C, 3, nullptr, nullptr, nullptr, nullptr, v.H / 2, v.W / 2,
                   v.H / 4, v.W / 4, 3, 2, 1, nullptr, nullptr, fp(work), st, fp(pre_slab),
-                  (int)pre_rows, nullptr);
+                  (int)pre_rows, nullptr, bn_sums.has_value() ? 2 : 0,
+                  bn_sums.has_value() ? need_f64(*bn_sums, "sums", 2 * C) : nullptr,
+                  bn_total.has_value() ? need_f64(*bn_total, "total", 1) : nullptr);
   float* d_part = fp(dslab);
   float* g_part = d_part + grid * C * dm::stem_slab_cols();
   float* sums = g_part + grid * dm::stem_gram_cols() * dm::stem_gram_cols();
@@ -897,7 +982,16 @@ void register_resnet(pybind11::module_& m) {
         py::arg("xs"), py::arg("Cin"), py::arg("dw"), py::arg("wbeta"), py::arg("work"),
         py::arg("slab"));
   m.def("bn_backward", &bn_backward, py::arg("dout"), py::arg("out"), py::arg("y"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"), py::arg("dgamma"), py::arg("dbeta"), py::arg("gbeta"), py::arg("mode"), py::arg("scale"), py::arg("shift"), py::arg("pdy"), py::arg("pidx"), py::arg("K"), py::arg("S"), py::arg("P"), py::arg("dy"), py::arg("dres"), py::arg("work"),
-        py::arg("pre_slab") = py::none(), py::arg("pre_rows") = 0, py::arg("mask") = py::none());
+        py::arg("pre_slab") = py::none(), py::arg("pre_rows") = 0, py::arg("mask") = py::none(),
+        py::arg("stage") = 0, py::arg("sums") = py::none(), py::arg("total") = py::none());
+  m.def("bn_bwd_sums", &bn_bwd_sums, py::arg("pre_slab"), py::arg("pre_rows"), py::arg("C"),
+        py::arg("dgamma"), py::arg("dbeta"), py::arg("gbeta"), py::arg("work"), py::arg("sums"));
+  m.def("bn_sync_local", &bn_sync_local, py::arg("stats"), py::arg("T"), py::arg("count"),
+        py::arg("C"), py::arg("row"), py::arg("work"));
+  m.def("bn_sync_finalize", &bn_sync_finalize, py::arg("rows"), py::arg("gamma"), py::arg("beta"),
+        py::arg("rmean"), py::arg("rvar"), py::arg("momentum"), py::arg("eps"), py::arg("scale"),
+        py::arg("shift"), py::arg("mean"), py::arg("invstd"), py::arg("num_batches"),
+        py::arg("total"));
   m.def("bn_relu_maxpool", &bn_relu_maxpool, py::arg("y"), py::arg("scale"), py::arg("shift"),
         py::arg("out"), py::arg("idx"), py::arg("K"), py::arg("S"), py::arg("P"),
         py::arg("yarg") = py::none());
@@ -923,6 +1017,7 @@ void register_resnet(pybind11::module_& m) {
         py::arg("nbi"), py::arg("wk"), py::arg("pdy"), py::arg("code4"), py::arg("mean"),
         py::arg("invstd"), py::arg("gamma"), py::arg("dgamma"), py::arg("dbeta"),
         py::arg("gbeta"), py::arg("pre_slab"), py::arg("pre_rows"), py::arg("dw"),
-        py::arg("wbeta"), py::arg("work"), py::arg("dslab"), py::arg("grid"));
+        py::arg("wbeta"), py::arg("work"), py::arg("dslab"), py::arg("grid"),
+        py::arg("sums") = py::none(), py::arg("total") = py::none());
   m.def("stem_pack_weights", &stem_pack_weights);
 }

@@ -180,6 +180,101 @@ __global__ void __launch_bounds__(NT) bn_finalize_kernel(const float* __restrict
   fin_fwd_channel(f, c, s, q, count);
 }
 
+// ------------------------------------------------------------------ cross-rank BatchNorm
+// Synchronized BatchNorm splits every finalize at its sums.  Forward: each rank turns its
+// statistics slab into ONE float64 row [mean_r (C) | M2_r (C) | n_r] (bn_sync_local), the
+// rows of all ranks are gathered, and every rank merges them in rank order in double
+// (bn_sync_finalize: same rows, same order -> bit-identical results everywhere).  Counts and
+// transport stay exact in float64; N never leaves the device.
+template <int NT, int CH>
+__global__ void __launch_bounds__(NT) bn_sync_local_kernel(const float* __restrict__ part, int G,
+                                                           int C, double count,
+                                                           double* __restrict__ row) {
+  const int c = blockIdx.x * CH + (threadIdx.x % CH);
+  if (blockIdx.x == 0 && threadIdx.x == 0) row[2 * C] = count;
+  double s, q;
+  block_sum2<NT, CH>(part, G, C, c, s, q);
+  if (threadIdx.x >= CH || c >= C) return;
+  double m2 = q - s * s / count;
+  if (m2 < 0) m2 = 0;
+  row[c] = s / count;
+  row[C + c] = m2;
+}
+
+// rows: [ws][2C+1]; one thread per channel, the ws rows merged in rank order
+__global__ void __launch_bounds__(256) bn_sync_finalize_kernel(const double* __restrict__ rows,
+                                                               int ws, int C, FinFwd f,
+                                                               double* __restrict__ total) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const long long L = 2LL * C + 1;
+  double N = 0.0, sm = 0.0;
+  for (int r = 0; r < ws; ++r) {
+    const double n = rows[r * L + 2 * C];
+    N += n;
+    sm += n * rows[r * L + c];
+  }
+  const double mean = sm / N;
+  double M2 = 0.0;
+  for (int r = 0; r < ws; ++r) {
+    const double n = rows[r * L + 2 * C];
+    const double d = rows[r * L + c] - mean;
+    M2 += rows[r * L + C + c] + n * d * d;
+  }
+  const double var = M2 / N;
+  const float invstd = (float)(1.0 / sqrt(var + f.eps));
+  const float sc = f.gamma[c] * invstd;
+  f.scale[c] = sc;
+  f.shift[c] = f.beta[c] - (float)mean * sc;
+  f.mean_out[c] = (float)mean;
+  f.invstd_out[c] = invstd;
+  if (f.rmean) {
+    const double unbiased = N > 1 ? var * N / (N - 1) : var;
+    f.rmean[c] = (1.f - f.momentum) * f.rmean[c] + f.momentum * (float)mean;
+    f.rvar[c] = (1.f - f.momentum) * f.rvar[c] + f.momentum * (float)unbiased;
+  }
+  if (c == 0) {
+    *total = N;
+    if (f.num_batches) *f.num_batches += 1;
+  }
+}
+
+// Backward stage "sums": this rank's Σdz, Σdz·x̂ -> dgamma / dbeta (local sums: the data-
+// parallel gradient average makes them global) and sums [2C] float64 for the cross-rank add.
+template <int NT, int CH>
+__global__ void __launch_bounds__(NT) bn_bwd_sums_kernel(const float* __restrict__ part, int G,
+                                                         int C, float* __restrict__ dgamma,
+                                                         float* __restrict__ dbeta, float gbeta,
+                                                         double* __restrict__ sums) {
+  const int c = blockIdx.x * CH + (threadIdx.x % CH);
+  double s, q;
+  block_sum2<NT, CH>(part, G, C, c, s, q);
+  if (threadIdx.x >= CH || c >= C) return;
+  dbeta[c] = (gbeta != 0.f ? gbeta * dbeta[c] : 0.f) + (float)s;
+  dgamma[c] = (gbeta != 0.f ? gbeta * dgamma[c] : 0.f) + (float)q;
+  sums[c] = s;
+  sums[C + c] = q;
+}
+
+// Backward stage "apply": the coefficients a, b, c of dy = a·dz + b·y + c from the global sums
+// and the global element count (a device scalar), as fin_bwd_channel computes them.
+__global__ void __launch_bounds__(256) bn_bwd_coef_kernel(const double* __restrict__ sums,
+                                                          const double* __restrict__ total,
+                                                          const float* __restrict__ gamma,
+                                                          const float* __restrict__ mean,
+                                                          const float* __restrict__ invstd, int C,
+                                                          float* __restrict__ coef) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const float a = gamma[c] * invstd[c];
+  const float inv_m = (float)(1.0 / *total);
+  const float b = -a * invstd[c] * (float)sums[C + c] * inv_m;
+  const float cc = -a * (float)sums[c] * inv_m - b * mean[c];
+  coef[c] = a;
+  coef[C + c] = b;
+  coef[2 * C + c] = cc;
+}
+
 // eval mode: scale/shift from running stats
 __global__ void bn_eval_coeffs_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
                                       const float* __restrict__ rmean, const float* __restrict__ rvar,
@@ -1143,6 +1238,31 @@ void bn_stats_finalize(const float* stats, int T, int C, double count, const flo
     bn_finalize_kernel<256, FIN_CH><<<(C + FIN_CH - 1) / FIN_CH, 256, 0, st>>>(fin, rows, C, count, f);
 }
 
+void bn_sync_local(const float* stats, int T, int C, double count, double* row, float* work,
+                   hipStream_t st) {
+  const int W = 2 * C;
+  const int G = colsum_groups(T);
+  const float* fin = stats;
+  if (G) {
+    slab_colsum_kernel<<<dim3((W + 63) / 64, G), 256, 0, st>>>(stats, T, W, work);
+    fin = work;
+  }
+  const int rows = G ? G : T;
+  if (rows > 256)
+    bn_sync_local_kernel<256, 4><<<(C + 3) / 4, 256, 0, st>>>(fin, rows, C, count, row);
+  else
+    bn_sync_local_kernel<256, FIN_CH><<<(C + FIN_CH - 1) / FIN_CH, 256, 0, st>>>(fin, rows, C, count,
+                                                                          row);
+}
+
+void bn_sync_finalize(const double* rows, int ws, int C, const float* gamma, const float* beta,
+                      float* rmean, float* rvar, float momentum, float eps, float* scale,
+                      float* shift, float* mean, float* invstd, long long* num_batches,
+                      double* total, hipStream_t st) {
+  const FinFwd f{gamma, beta, rmean, rvar, momentum, eps, scale, shift, mean, invstd, num_batches};
+  bn_sync_finalize_kernel<<<(C + 255) / 256, 256, 0, st>>>(rows, ws, C, f, total);
+}
+
 void bn_eval_coeffs(const float* gamma, const float* beta, const float* rmean, const float* rvar,
                     float eps, int C, float* scale, float* shift, hipStream_t st) {
   bn_eval_coeffs_kernel<<<(C + 255) / 256, 256, 0, st>>>(gamma, beta, rmean, rvar, eps, C, scale,
@@ -1180,7 +1300,12 @@ void bn_backward(const bf16_t* dout, const bf16_t* out, const bf16_t* y, const f
                  float gbeta, long long M, int C, int mode, const float* scale,
                  const float* shift, const bf16_t* pdy, const uint8_t* pidx, int H, int W,
                  int OH, int OW, int K, int S, int P, bf16_t* dy, bf16_t* dres, float* work,
-                 hipStream_t st, const float* pre_part, int pre_rows, const uint8_t* mask) {
+                 hipStream_t st, const float* pre_part, int pre_rows, const uint8_t* mask,
+                 int stage, double* sums, const double* total) {
+  // stage (cross-rank BatchNorm): 0 = the whole backward; 1 = "sums": the reduction (or
+  // pre_part), dgamma / dbeta from this rank's sums, and sums [2C] float64 out -- nothing else;
+  // 2 = "apply": no reduction, dgamma / dbeta untouched, the coefficients from the global `sums`
+  // and the device scalar `total` into work[0, 3C), then the apply kernels as in stage 0
   // pre_part (optional): [pre_rows][2C] partial Σdz, Σdz·x̂ already reduced by the producing
   // kernel (the stem's pooled-domain sums) — the reduction pass over dout and y is skipped
   // work: [G][2C] partials + [3C] coefficients + [<=256][2C] second-level partials
@@ -1191,10 +1316,12 @@ void bn_backward(const bf16_t* dout, const bf16_t* out, const bf16_t* y, const f
                     OH == H / 2 && OW == W / 2 && !dres && (long long)M * C / 8 < (1LL << 31);
   const int G = pre_part ? pre_rows : quad ? bn_bwd_groups(M / 4, C) : bn_bwd_groups(M, C);
   float* part = pre_part ? const_cast<float*>(pre_part) : work;
-  float* coef = pre_part ? work : work + (long long)G * 2 * C;
+  float* coef = (pre_part || stage == 2) ? work : work + (long long)G * 2 * C;
   float* part2 = coef + 3 * C;
   const size_t shr = sizeof(float) * (256 * 16 + 2 * C);
-  if (pre_part) {
+  if (stage == 2) {
+    bn_bwd_coef_kernel<<<(C + 255) / 256, 256, 0, st>>>(sums, total, gamma, mean, invstd, C, coef);
+  } else if (pre_part) {
   } else if (quad) bn_bwd_reduce_quad_kernel<<<G, 256, shr, st>>>(a, part);
   else switch (mode) {
     // 4 16-B chunks per operand in flight per thread (8 measured neutral for the reduce and
@@ -1207,19 +1334,30 @@ void bn_backward(const bf16_t* dout, const bf16_t* out, const bf16_t* y, const f
     case 4: bn_bwd_reduce_kernel<4, 4, true><<<G, 256, shr, st>>>(a, part); break;
     default: bn_bwd_reduce_kernel<3><<<G, 256, shr, st>>>(a, part); break;
   }
-  const int G2 = colsum_groups(G);
-  const FinBwd fb{gamma, mean, invstd, dgamma, dbeta, gbeta, coef};
-  const float* fin = part;
-  if (G2) {  // parallel fixed-order pre-reduction so the finalize sums stay short
-    slab_colsum_kernel<<<dim3((2 * C + 63) / 64, G2), 256, 0, st>>>(part, G, 2 * C, part2);
-    fin = part2;
+  if (stage != 2) {
+    const int G2 = colsum_groups(G);
+    const FinBwd fb{gamma, mean, invstd, dgamma, dbeta, gbeta, coef};
+    const float* fin = part;
+    if (G2) {  // parallel fixed-order pre-reduction so the finalize sums stay short
+      slab_colsum_kernel<<<dim3((2 * C + 63) / 64, G2), 256, 0, st>>>(part, G, 2 * C, part2);
+      fin = part2;
+    }
+    const int rows = G2 ? G2 : G;
+    if (stage == 1) {
+      if (rows > 256)
+        bn_bwd_sums_kernel<256, 4><<<(C + 3) / 4, 256, 0, st>>>(fin, rows, C, dgamma, dbeta, gbeta,
+                                                                sums);
+      else
+        bn_bwd_sums_kernel<256, FIN_CH><<<(C + FIN_CH - 1) / FIN_CH, 256, 0, st>>>(
+            fin, rows, C, dgamma, dbeta, gbeta, sums);
+      return;
+    }
+    if (rows > 256)
+      bn_bwd_finalize_kernel<256, 4><<<(C + 3) / 4, 256, 0, st>>>(fin, rows, C, (double)M, fb);
+    else
+      bn_bwd_finalize_kernel<256, FIN_CH><<<(C + FIN_CH - 1) / FIN_CH, 256, 0, st>>>(fin, rows, C,
+                                                                              (double)M, fb);
   }
-  const int rows = G2 ? G2 : G;
-  if (rows > 256)
-    bn_bwd_finalize_kernel<256, 4><<<(C + 3) / 4, 256, 0, st>>>(fin, rows, C, (double)M, fb);
-  else
-    bn_bwd_finalize_kernel<256, FIN_CH><<<(C + FIN_CH - 1) / FIN_CH, 256, 0, st>>>(fin, rows, C,
-                                                                            (double)M, fb);
   if (!dy) return;  // coefficients only: stem_bwd_fused / stem_bwd_fused2 apply dy themselves
   const long long n8 = M * C / 8;
   // grid-strided mode 3: workgroup cap 4096 (1024-8192 within noise,

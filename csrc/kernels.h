@@ -224,7 +224,16 @@ void bn_backward(const bf16_t* dout, const bf16_t* out, const bf16_t* y, const f
                  const float* shift, const bf16_t* pdy, const uint8_t* pidx, int H, int W,
                  int OH, int OW, int K, int S, int P, bf16_t* dy, bf16_t* dres, float* work,
                  hipStream_t st, const float* pre_part = nullptr, int pre_rows = 0,
-                 const uint8_t* mask = nullptr);
+                 const uint8_t* mask = nullptr, int stage = 0, double* sums = nullptr,
+                 const double* total = nullptr);
+// cross-rank BatchNorm forward: this rank's float64 row [mean (C) | M2 (C) | n] from its
+// statistics slab; then the merge of all ranks' rows [ws][2C+1] in rank order (total = Σn)
+void bn_sync_local(const float* stats, int T, int C, double count, double* row, float* work,
+                   hipStream_t st);
+void bn_sync_finalize(const double* rows, int ws, int C, const float* gamma, const float* beta,
+                      float* rmean, float* rvar, float momentum, float eps, float* scale,
+                      float* shift, float* mean, float* invstd, long long* num_batches,
+                      double* total, hipStream_t st);
 void bn_relu_maxpool(const bf16_t* y, const float* scale, const float* shift, bf16_t* out,
                      uint8_t* idx, int N, int H, int W, int C, int OH, int OW, int K, int S,
                      int P, hipStream_t st, bf16_t* yarg = nullptr);

@@ -24,7 +24,10 @@ class ResNet18(Program):
     accepts_gathered = True
 
     def __init__(self, num_classes: int = 1000, in_channels: int = 3,
-                 widths=(64, 128, 256, 512)):
+                 widths=(64, 128, 256, 512), sync_bn=False):
+        """``sync_bn``: BatchNorm statistics over every rank's shard
+        (:func:`dmlab.nn.convert_sync_batchnorm`; every rank must then construct the model:
+        a dedicated process group is created).  ``"force"`` runs that path at one rank too."""
         super().__init__()
         # stem = conv7x7/s2 + BN + ReLU + maxpool3x3/s2 (one fused layer)
         self.stem = ConvBNPool(in_channels, widths[0], 7, 2, 3, pool_k=3, pool_s=2, pool_p=1)
@@ -44,6 +47,10 @@ class ResNet18(Program):
         self.build(layers)
         # conv weight gradients run on a second stream, overlapping the dgrad/BN chain
         self._uses_side_stream = True
+        if sync_bn:
+            from dmlab.nn.syncbn import convert_sync_batchnorm
+
+            convert_sync_batchnorm(self, force=sync_bn == "force")
 
     def prepare_native(self, x):
         if self.compute_dtype != torch.bfloat16:

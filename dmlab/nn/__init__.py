@@ -3,7 +3,8 @@ from .layers import (BasicBlock, Conv2d, ConvBN, ConvBNPool, Flatten, GlobalAvgP
                      MaxPool, Softmax)
 from .loss import CrossEntropyLoss, EvalMetrics, count_correct, cross_entropy
 from .program import Ctx, Layer, Program
+from .syncbn import convert_sync_batchnorm
 
-__all__ = ["FlatParams", "Program", "Layer", "Ctx", "Conv2d", "Linear", "Flatten", "Softmax",
+__all__ = ["convert_sync_batchnorm", "FlatParams","Program", "Layer", "Ctx", "Conv2d", "Linear", "Flatten", "Softmax",
            "ConvBN", "ConvBNPool", "BasicBlock", "MaxPool", "GlobalAvgPool", "CrossEntropyLoss",
            "cross_entropy", "count_correct", "EvalMetrics"]

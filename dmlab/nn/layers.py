@@ -128,6 +128,10 @@ class ConvBN(Layer):
     reduced in the conv epilogue, then one fused BN-apply/residual/ReLU pass
     (SURVEY §2.5 'Extensions required by BASELINE.json')."""
 
+    # dmlab.nn.syncbn.SyncBNState once convert_sync_batchnorm marked the layer: training-mode
+    # statistics then span every rank of its group (both paths); None = per-rank statistics
+    _sync_bn = None
+
     def __init__(self, cin, cout, k, stride=1, padding=0, relu=True, eps=1e-5, momentum=0.1):
         super().__init__()
         self.cin, self.cout, self.k, self.stride, self.padding = cin, cout, k, stride, padding
@@ -145,8 +149,13 @@ class ConvBN(Layer):
         y = F.conv2d(x, self.weight, None, self.stride, self.padding)
         if self.training:
             self.num_batches_tracked.add_(1)
-        y = F.batch_norm(y, self.running_mean, self.running_var, self.bn_weight, self.bn_bias,
-                         self.training, self.momentum, self.eps)
+        if self.training and self._sync_bn is not None:
+            from .syncbn import sync_batch_norm
+
+            y = sync_batch_norm(y, self)  # batch statistics over every rank's shard
+        else:
+            y = F.batch_norm(y, self.running_mean, self.running_var, self.bn_weight,
+                             self.bn_bias, self.training, self.momentum, self.eps)
         if residual is not None:
             y = y + residual
         return F.relu(y) if self.relu else y

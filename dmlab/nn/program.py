@@ -337,6 +337,13 @@ class Program(nn.Module):
         self._anchor.requires_grad_(True)
         return self
 
+    @property
+    def sync_bn_collectives(self) -> int:
+        """Synchronized-BatchNorm collectives issued so far (0 for a program that
+        :func:`dmlab.nn.convert_sync_batchnorm` did not convert)."""
+        st = getattr(self, "_sync_bn_state", None)
+        return st.collectives if st is not None else 0
+
     def set_backend(self, backend: str):
         assert backend in ("auto", "torch", "native")
         self.backend = backend

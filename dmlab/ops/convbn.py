@@ -275,6 +275,28 @@ def stem_fused_ok(layer, x):
     return bool(lib().stem_fused_supported(H, W))
 
 
+def _bn_finalize(L, layer, stats, T, M, scale, shift, mean, invstd, work):
+    """Statistics slab [T][2C] -> scale / shift / mean / invstd + the running statistics.
+    Per-rank BatchNorm: one finalize over this rank's M elements, returns None.  Synchronized
+    (dmlab.nn.syncbn): local float64 row -> all-gather -> merge in rank order; returns the
+    global element count as a float64 device scalar (it never visits the host)."""
+    g, b = layer.bn_weight.detach(), layer.bn_bias.detach()
+    sync = layer._sync_bn
+    if sync is None:
+        L.bn_stats_finalize(stats, T, float(M), g, b, layer.running_mean, layer.running_var,
+                            layer.momentum, layer.eps, scale, shift, mean, invstd, work,
+                            layer.num_batches_tracked)
+        return None
+    C = layer.cout
+    row = torch.empty(2 * C + 1, device=stats.device, dtype=torch.float64)
+    L.bn_sync_local(stats, T, float(M), C, row, work)
+    rows = sync.gather_rows(row)
+    total = torch.empty(1, device=stats.device, dtype=torch.float64)
+    L.bn_sync_finalize(rows, g, b, layer.running_mean, layer.running_var, layer.momentum,
+                       layer.eps, scale, shift, mean, invstd, layer.num_batches_tracked, total)
+    return total
+
+
 def _stem_fused_fwd(layer, x, ctx, train):
     """Fused stem forward: pooled BN-input extremum + window codes + BN statistics in one
     kernel, then BN + ReLU on the pooled tensor.  The conv output is never written."""
@@ -298,14 +320,12 @@ def _stem_fused_fwd(layer, x, ctx, train):
     stats = torch.empty(grid * 128, **f32) if use_batch else None
     L.stem_fwd_fused(img, idx, nsc, nbi, wk, layer.bn_weight.detach(), pext, code, stats, grid)
     M = B * (H // 2) * (W // 2)
+    total = None
     if use_batch:
         mean = torch.empty(64, **f32)
         invstd = torch.empty(64, **f32)
         work = torch.empty(256 * 2 * 64, **f32)
-        L.bn_stats_finalize(stats, grid, float(M), layer.bn_weight.detach(),
-                            layer.bn_bias.detach(), layer.running_mean, layer.running_var,
-                            layer.momentum, layer.eps, scale, shift, mean, invstd, work,
-                            layer.num_batches_tracked)
+        total = _bn_finalize(L, layer, stats, grid, M, scale, shift, mean, invstd, work)
     else:
         L.bn_eval_coeffs(layer.bn_weight.detach(), layer.bn_bias.detach(), layer.running_mean,
                          layer.running_var, layer.eps, scale, shift)
@@ -316,7 +336,7 @@ def _stem_fused_fwd(layer, x, ctx, train):
     if train:
         ctx.update(fused_stem=True, img=img, gidx=idx, nsc=nsc, nbi=nbi, wk=wk, yarg=pext,
                    idx=code4, mean=mean, invstd=invstd, scale=scale, shift=shift, has_res=False,
-                   first=True, s2d=False, pre=None, y=pext, x=None, M=M)
+                   first=True, s2d=False, pre=None, y=pext, x=None, M=M, total=total)
     return out
 
 
@@ -340,11 +360,20 @@ def _stem_fused_bwd(layer, dout, ctx):
     f32 = dict(device=dout.device, dtype=torch.float32)
     work = torch.empty(L.bn_bwd_work(ctx["M"], 64), **f32)
     dslab = torch.empty(L.stem_bwd_slab_len(grid), **f32)
+    sync_kw = {}
+    if ctx.get("total") is not None:
+        # synchronized BatchNorm: dgamma / dbeta from this rank's sums, the coefficients from
+        # the sums of every rank and the global count
+        sums = torch.empty(128, device=dout.device, dtype=torch.float64)
+        L.bn_bwd_sums(pre_sums["pre_slab"], pre_sums["pre_rows"], 64, layer.grad_slot("bn_weight"),
+                      layer.grad_slot("bn_bias"), acc, work, sums)
+        layer._sync_bn.reduce_sums(sums)
+        sync_kw = dict(sums=sums, total=ctx["total"])
     L.stem_bwd_fused2(ctx["img"], ctx["gidx"], ctx["nsc"], ctx["nbi"], ctx["wk"], dout, code,
                       ctx["mean"], ctx["invstd"], layer.bn_weight.detach(),
                       layer.grad_slot("bn_weight"), layer.grad_slot("bn_bias"), acc,
                       pre_sums["pre_slab"], pre_sums["pre_rows"], layer.grad_slot("weight"), acc,
-                      work, dslab, grid)
+                      work, dslab, grid, **sync_kw)
     return None
 
 
@@ -463,6 +492,7 @@ def convbn_fwd(layer, x, ctx, train, residual=None, raw=False, pre=None):
     scale = torch.empty(cout, **f32)
     shift = torch.empty(cout, **f32)
     use_batch = layer.training
+    total = None
     if use_batch:
         T = L.conv_stats_rows(M, cfg)
         stats = torch.empty(T * 2 * cout, **f32)
@@ -470,9 +500,7 @@ def convbn_fwd(layer, x, ctx, train, residual=None, raw=False, pre=None):
         mean = torch.empty(cout, **f32)
         invstd = torch.empty(cout, **f32)
         work = torch.empty(256 * 2 * cout, **f32)
-        L.bn_stats_finalize(stats, T, float(M), layer.bn_weight.detach(), layer.bn_bias.detach(),
-                            layer.running_mean, layer.running_var, layer.momentum, layer.eps,
-                            scale, shift, mean, invstd, work, layer.num_batches_tracked)
+        total = _bn_finalize(L, layer, stats, T, M, scale, shift, mean, invstd, work)
     else:
         L.conv_fwd(x, wf, y, None, None, k, k, s, p, cfg, **pre_kw)
         L.bn_eval_coeffs(layer.bn_weight.detach(), layer.bn_bias.detach(), layer.running_mean,
@@ -480,7 +508,7 @@ def convbn_fwd(layer, x, ctx, train, residual=None, raw=False, pre=None):
         mean = invstd = None
     if train:
         ctx.update(x=x, y=y, mean=mean, invstd=invstd, has_res=residual is not None,
-                   first=first, s2d=s2d, scale=scale, shift=shift, pre=pre)
+                   first=first, s2d=s2d, scale=scale, shift=shift, pre=pre, total=total)
     if raw:
         ctx["scale"], ctx["shift"] = scale, shift
         return y
@@ -615,8 +643,11 @@ def convbn_bwd(layer, dout, ctx, need_dx, dx_add=None, dx_into=None, fused_skip=
         rows = L.bn_bwd_reduce_masked(dout, ctx["yarg"], ctx["mean"], ctx["invstd"], ctx["scale"],
                                       ctx["shift"], part)
         pre_sums = dict(pre_slab=part, pre_rows=rows)
+    # synchronized BatchNorm (ctx["total"]: the global count of the forward's merge): the
+    # space-to-depth stem takes the unfused mode-3 backward below, which has the two stages
+    total = ctx.get("total")
     stem_ok = (pool and s2d and pre_sums and ctx["first"] and not ctx["has_res"]
-               and L.stem_bwd_fused_supported(y, x))
+               and total is None and L.stem_bwd_fused_supported(y, x))
     if stem_ok:
         # stem: BN-backward apply fused into the s2d weight gradient -- the full-resolution
         # dy is never written (csrc/conv_stem.hip stem_wgrad_ws_kernel)
@@ -656,13 +687,23 @@ def convbn_bwd(layer, dout, ctx, need_dx, dx_add=None, dx_into=None, fused_skip=
     else:
         dy = empty_nhwc(N, OH, OW, cout, y)
         dres = empty_nhwc(N, OH, OW, cout, y) if (ctx["has_res"] and not masked_res) else None
-        L.bn_backward(None if pool else dout, ctx.get("out"), y, ctx["mean"], ctx["invstd"],
-                      layer.bn_weight.detach(), layer.grad_slot("bn_weight"),
-                      layer.grad_slot("bn_bias"), acc, mode, ctx["scale"], ctx["shift"],
-                      dout if pool else None, ctx.get("idx"),
-                      getattr(layer, "pool_k", 3), getattr(layer, "pool_s", 2),
-                      getattr(layer, "pool_p", 1), dy, dres, work,
-                      mask=in_mask if in_mask is not None else ctx.get("mask"), **pre_sums)
+        bn_args = (None if pool else dout, ctx.get("out"), y, ctx["mean"], ctx["invstd"],
+                   layer.bn_weight.detach(), layer.grad_slot("bn_weight"),
+                   layer.grad_slot("bn_bias"), acc, mode, ctx["scale"], ctx["shift"],
+                   dout if pool else None, ctx.get("idx"),
+                   getattr(layer, "pool_k", 3), getattr(layer, "pool_s", 2),
+                   getattr(layer, "pool_p", 1), dy, dres, work)
+        bn_mask = in_mask if in_mask is not None else ctx.get("mask")
+        if total is None:
+            L.bn_backward(*bn_args, mask=bn_mask, **pre_sums)
+        else:
+            # stage "sums": this rank's Σdz, Σdz·x̂ (reduced here or taken from pre_sums) ->
+            # dgamma / dbeta and a float64 row; all-reduce; stage "apply": the coefficients
+            # from the global sums and count, then the same apply kernels
+            sums = torch.empty(2 * cout, device=y.device, dtype=torch.float64)
+            L.bn_backward(*bn_args, mask=bn_mask, stage=1, sums=sums, **pre_sums)
+            layer._sync_bn.reduce_sums(sums)
+            L.bn_backward(*bn_args, mask=bn_mask, stage=2, sums=sums, total=total)
         if phase == 1:
             ctx["_bn_out"] = (dy, dres)
             return None

@@ -114,7 +114,15 @@ def parse_args(argv=None):
     p.add_argument("--graph", default="auto", choices=["auto", "0", "1"],
                    help="capture the fused step (with its all-reduce) in a hipGraph (auto: "
                         "on when --fused is, unless the group is gloo at ws > 1)")
-    return p.parse_args(argv)
+    p.add_argument("--sync-bn", default="off", choices=["off", "on", "force"],
+                   help="resnet18: BatchNorm statistics over every rank's shard (one small "
+                        "all-gather per layer and forward, one all-reduce per layer and "
+                        "backward, on a process group of their own); force: also at one rank, "
+                        "so a one-GPU box runs the multi-rank kernels and collectives")
+    a = p.parse_args(argv)
+    if a.sync_bn != "off" and a.model == "lenet":
+        p.error("--sync-bn needs --model resnet18 (LeNet has no BatchNorm)")
+    return a
 
 
 def main(argv=None):
@@ -216,6 +224,10 @@ def main(argv=None):
         from dmlab.utils import checkpoint
 
         resumed = checkpoint.load(a.resume, model, opt)
+    if a.sync_bn != "off":  # before DDP wraps the model; every rank (creates a process group)
+        from dmlab.nn import convert_sync_batchnorm
+
+        convert_sync_batchnorm(model, force=a.sync_bn == "force")
     if a.dp == "ddp":
         net = DDP(model, bucket_cap_mb=a.bucket_mb,  # broadcasts rank-0 params
                   small_allreduce="xgmi" if a.allreduce == "xgmi" and dev.type == "cuda" else None,
@@ -293,6 +305,8 @@ def main(argv=None):
     elif not a.no_test and a.topk == 0 and rank == 0:
         stats["accuracy"] = test(model, DeviceLoader(test_set.to(dev, dtype=act), 32, **ev_kw))
     stats.update(checks)
+    if a.sync_bn != "off":
+        stats.update(sync_bn=a.sync_bn, sync_bn_collectives=model.sync_bn_collectives)
     stats.update(rank=rank, world_size=ws, sampler=a.sampler, dp=a.dp, compress=a.compress,
                  comm_bytes_per_step=(net.comm_bytes_per_step if a.dp == "ddp"
                                       else agg.bytes_per_call),
