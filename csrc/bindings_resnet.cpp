@@ -513,6 +513,12 @@ void bn_sync_finalize(at::Tensor rows, at::Tensor gamma, at::Tensor beta,
 void bn_eval_coeffs(at::Tensor gamma, at::Tensor beta, at::Tensor rmean, at::Tensor rvar, double eps,
                     at::Tensor scale, at::Tensor shift) {
   const int C = gamma.numel();
+  TORCH_CHECK(C >= 1, "bn_eval_coeffs: C >= 1");
+  for (auto* t : {&gamma, &beta, &rmean, &rvar, &scale, &shift}) {
+    need_f32(*t, "bn vec");
+    TORCH_CHECK(t->numel() == C && t->device() == gamma.device(),
+                "bn_eval_coeffs: six fp32 vectors of C elements on one device");
+  }
   const DeviceGuard guard(gamma.device());
   dm::bn_eval_coeffs(fp(gamma), fp(beta), fp(rmean), fp(rvar), eps, C, fp(scale), fp(shift),
                      cur_stream());
@@ -523,6 +529,7 @@ void bn_apply(at::Tensor y, c10::optional<at::Tensor> res, at::Tensor scale, at:
   need_bf16_nhwc(y, "y");
   need_bf16_nhwc(out, "out");
   const int C = y.size(3);
+  ilog2(C / 8);  // the kernel takes a chunk's channel as i & (C/8 - 1)
   need_f32(scale, "scale", C);
   need_f32(shift, "shift", C);
   const bf* rp = nullptr;
@@ -669,7 +676,11 @@ void bn_backward(c10::optional<at::Tensor> dout, c10::optional<at::Tensor> out, 
     mp = (const uint8_t*)mask->data_ptr();
   }
   bf* drp = nullptr;
-  if (dres.has_value()) { need_bf16_nhwc(*dres, "dres"); drp = bp(*dres); }
+  if (dres.has_value()) {
+    need_bf16_nhwc(*dres, "dres");
+    TORCH_CHECK(dres->sizes() == y.sizes(), "dres: the shape of y");
+    drp = bp(*dres);
+  }
   const DeviceGuard guard(y.device());
   dm::bn_backward(doutp, outp, bp(y), fp(mean), fp(invstd), fp(gamma), fp(dgamma), fp(dbeta),
                   (float)gbeta, M, C, (int)mode, scp, shp, pdyp, pidxp, y.size(1), y.size(2), OH,
@@ -738,10 +749,27 @@ int64_t bn_bwd_reduce_masked(at::Tensor dout, at::Tensor y, at::Tensor mean, at:
 }
 
 // ------------------------------------------------------------------ pooling / packing
+// x [N][H][W][C] and its KxK / stride S / pad P pooled tensor y, with the argmax codes idx
+// (kh*K + kw in one byte; 15 is the fused stem tail's "no gradient" code)
+void need_maxpool(const at::Tensor& x, const at::Tensor& y, const at::Tensor& idx, int64_t K,
+                  int64_t S, int64_t P) {
+  TORCH_CHECK(K >= 1 && S >= 1 && P >= 0 && 2 * P <= K && K * K <= 255,
+              "max pool: K, S >= 1, 0 <= 2P <= K, K*K <= 255");
+  TORCH_CHECK(x.size(1) + 2 * P >= K && x.size(2) + 2 * P >= K, "max pool: window larger than input");
+  TORCH_CHECK(y.size(0) == x.size(0) && y.size(3) == x.size(3), "max pool: N and C must agree");
+  TORCH_CHECK(y.size(1) == (x.size(1) + 2 * P - K) / S + 1 &&
+              y.size(2) == (x.size(2) + 2 * P - K) / S + 1,
+              "max pool: the pooled extent must be (H + 2P - K) / S + 1");
+  TORCH_CHECK(y.device() == x.device() && idx.device() == x.device(), "max pool: one device");
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == at::kByte && idx.is_contiguous() &&
+              idx.numel() == y.numel(), "idx: contiguous uint8, one code per pooled element");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(idx.data_ptr()) & 7) == 0, "idx must be 8-B aligned");
+}
+
 void maxpool_fwd(at::Tensor x, at::Tensor y, at::Tensor idx, int64_t K, int64_t S, int64_t P) {
   need_bf16_nhwc(x, "x");
   need_bf16_nhwc(y, "y");
-  TORCH_CHECK(idx.scalar_type() == at::kByte && idx.numel() == y.numel());
+  need_maxpool(x, y, idx, K, S, P);
   const DeviceGuard guard(x.device());
   dm::maxpool_fwd(bp(x), bp(y), (uint8_t*)idx.data_ptr(), x.size(0), x.size(1), x.size(2), x.size(3),
                   y.size(1), y.size(2), K, S, P, cur_stream());
@@ -750,6 +778,7 @@ void maxpool_fwd(at::Tensor x, at::Tensor y, at::Tensor idx, int64_t K, int64_t 
 void maxpool_bwd(at::Tensor dy, at::Tensor idx, at::Tensor dx, int64_t K, int64_t S, int64_t P) {
   need_bf16_nhwc(dy, "dy");
   need_bf16_nhwc(dx, "dx");
+  need_maxpool(dx, dy, idx, K, S, P);
   const DeviceGuard guard(dy.device());
   dm::maxpool_bwd(bp(dy), (const uint8_t*)idx.data_ptr(), bp(dx), dx.size(0), dx.size(1), dx.size(2),
                   dx.size(3), dy.size(1), dy.size(2), K, S, P, cur_stream());
@@ -758,6 +787,9 @@ void maxpool_bwd(at::Tensor dy, at::Tensor idx, at::Tensor dx, int64_t K, int64_
 void avgpool_fwd(at::Tensor x, at::Tensor y) {
   need_bf16_nhwc(x, "x");
   TORCH_CHECK(y.scalar_type() == at::kBFloat16 && y.numel() == x.size(0) * x.size(3));
+  TORCH_CHECK(y.is_cuda() && y.is_contiguous() && y.device() == x.device(),
+              "avgpool_fwd: y must be contiguous and on x's device");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(y.data_ptr()) & 15) == 0, "y must be 16-B aligned");
   const DeviceGuard guard(x.device());
   dm::avgpool_fwd(bp(x), bp(y), x.size(0), x.size(1) * x.size(2), x.size(3), cur_stream());
 }
@@ -765,6 +797,8 @@ void avgpool_fwd(at::Tensor x, at::Tensor y) {
 void avgpool_bwd(at::Tensor dy, at::Tensor dx) {
   need_bf16_nhwc(dx, "dx");
   TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && dy.is_contiguous() && dy.numel() == dx.size(0) * dx.size(3));
+  TORCH_CHECK(dy.is_cuda() && dy.device() == dx.device(), "avgpool_bwd: dy must be on dx's device");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(dy.data_ptr()) & 15) == 0, "dy must be 16-B aligned");
   const DeviceGuard guard(dx.device());
   dm::avgpool_bwd(bp(dy), bp(dx), dx.size(0), dx.size(1) * dx.size(2), dx.size(3), cur_stream());
 }
