@@ -214,99 +214,188 @@ inline const void* optp(const c10::optional<at::Tensor>& t) {
   return (t.has_value() && t->defined()) ? t->data_ptr() : nullptr;
 }
 
-void conv_small_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias, at::Tensor y,
-                    c10::optional<at::Tensor> mask, int64_t pad, int64_t pool, bool relu) {
-  check_act(x, "x"); check_act(y, "y"); CHECK_F32(w); CHECK_CONTIG(w);
-  TORCH_CHECK(x.dim() == 4 && w.dim() == 4 && w.size(1) == x.size(1) && w.size(2) == w.size(3));
-  TORCH_CHECK(is_bf16(x) == is_bf16(y), "x/y dtype mismatch");
-  const int B = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
-  const int Cout = w.size(0), K = w.size(2);
-  TORCH_CHECK(K == 3 || K == 5, "conv_small supports K in {3,5}");
-  TORCH_CHECK(pool == 1 || pool == 2, "pool must be 1 or 2");
-  const int OH = H + 2 * pad - K + 1, OW = W + 2 * pad - K + 1;
-  TORCH_CHECK(y.size(0) == B && y.size(1) == Cout && y.size(2) == OH / pool && y.size(3) == OW / pool,
-              "y shape mismatch");
-  if (pool > 1) TORCH_CHECK(mask.has_value() && mask->numel() == y.numel(), "mask required");
-  const DeviceGuard guard(x.device());
-  dm::conv_small_fwd(x.data_ptr(), w.data_ptr<float>(),
-                     bias.has_value() ? bias->data_ptr<float>() : nullptr, y.data_ptr(),
-                     pool > 1 ? (uint8_t*)mask->data_ptr() : nullptr, B, Cin, H, W, Cout, K,
-                     (int)pad, (int)pool, relu ? 1 : 0, is_bf16(x), cur_stream());
+// every tensor of one call lives on the device of the first
+inline void check_same_dev(const at::Tensor& ref, const at::Tensor& t, const char* n) {
+  TORCH_CHECK(t.is_cuda() && t.device() == ref.device(), n, " must be on the same device as ",
+              "the first operand (", ref.device(), "), got ", t.device());
+}
+inline bool has(const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); }
+inline void check_f32_vec(const at::Tensor& ref, const at::Tensor& t, int64_t n, const char* name) {
+  check_same_dev(ref, t, name);
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == n, name,
+              " must be a contiguous fp32 tensor of ", n, " elements");
+}
+inline void check_shape4(const at::Tensor& t, int64_t a, int64_t b, int64_t c, int64_t d,
+                         const char* name) {
+  TORCH_CHECK(t.dim() == 4 && t.size(0) == a && t.size(1) == b && t.size(2) == c && t.size(3) == d,
+              name, " shape mismatch: expected [", a, ", ", b, ", ", c, ", ", d, "], got ", t.sizes());
+}
+inline void check_pool_mask(const at::Tensor& ref, const c10::optional<at::Tensor>& mask,
+                            int64_t n) {
+  TORCH_CHECK(has(mask), "mask required with pool 2");
+  check_same_dev(ref, *mask, "mask");
+  TORCH_CHECK(mask->scalar_type() == at::kByte && mask->is_contiguous() && mask->numel() == n,
+              "mask must be a contiguous uint8 tensor of ", n, " elements (one per pooled element)");
 }
 
-void conv_small_bwd(at::Tensor x, at::Tensor w, at::Tensor dp, at::Tensor yp,
-                    c10::optional<at::Tensor> mask, c10::optional<at::Tensor> dx, at::Tensor dw,
-                    c10::optional<at::Tensor> db, at::Tensor work, int64_t pad, int64_t pool,
-                    bool relu, double beta, int64_t bs) {
-  check_act(x, "x"); check_act(dp, "dp"); check_act(yp, "yp");
-  CHECK_F32(w); CHECK_F32(dw); CHECK_F32(work);
-  const int B = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
-  const int Cout = w.size(0), K = w.size(2);
-  const int OH = H + 2 * pad - K + 1, OW = W + 2 * pad - K + 1;
-  const long long total = (long long)B * Cout * OH * OW;
-  const int S = (B + bs - 1) / bs;
-  const long long need = (total + 63) / 64 * 64 + (long long)S * (Cout * Cin * K * K + Cout);
-  TORCH_CHECK(work.numel() >= need, "workspace too small");
-  TORCH_CHECK(dw.numel() == w.numel(), "dw size");
-  if (dx.has_value()) { check_act(*dx, "dx"); TORCH_CHECK(dx->numel() == x.numel()); }
-  if (pool > 1) TORCH_CHECK(mask.has_value() && mask->numel() == dp.numel(), "mask required");
+// geometry shared by the two thin-conv bindings; refuses what the kernels have no template for
+struct SmallConvGeom { int B, Cin, H, W, Cout, K, OH, OW, PH, PW; };
+inline SmallConvGeom small_conv_geom(const at::Tensor& x, const at::Tensor& w, int64_t pad,
+                                     int64_t pool) {
+  check_act(x, "x");
+  check_same_dev(x, w, "w");
+  CHECK_F32(w); CHECK_CONTIG(w);
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 4 && w.size(1) == x.size(1) && w.size(2) == w.size(3),
+              "w must be [Cout, Cin, K, K] with x's Cin, got ", w.sizes(), " for x ", x.sizes());
+  TORCH_CHECK(x.numel() > 0 && w.size(0) >= 1, "empty x or w");
+  const int64_t K = w.size(2);
+  TORCH_CHECK(K == 3 || K == 5, "conv_small supports K in {3,5}, got ", K);
+  TORCH_CHECK(pool == 1 || pool == 2, "pool must be 1 or 2, got ", pool);
+  TORCH_CHECK(pad >= 0, "pad must be >= 0, got ", pad);
+  const int64_t OH = x.size(2) + 2 * pad - K + 1, OW = x.size(3) + 2 * pad - K + 1;
+  TORCH_CHECK(OH >= pool && OW >= pool, "image ", x.size(2), " x ", x.size(3),
+              " too small for K ", K, ", pad ", pad, ", pool ", pool);
+  return {(int)x.size(0), (int)x.size(1), (int)x.size(2), (int)x.size(3), (int)w.size(0), (int)K,
+          (int)OH, (int)OW, (int)(OH / pool), (int)(OW / pool)};
+}
+
+void conv_small_fwd(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias, at::Tensor y,
+                    c10::optional<at::Tensor> mask, int64_t pad, int64_t pool, bool relu) {
+  const SmallConvGeom g = small_conv_geom(x, w, pad, pool);
+  check_act(y, "y");
+  check_same_dev(x, y, "y");
+  TORCH_CHECK(is_bf16(x) == is_bf16(y), "x/y dtype mismatch");
+  check_shape4(y, g.B, g.Cout, g.PH, g.PW, "y");
+  if (has(bias)) check_f32_vec(x, *bias, g.Cout, "bias");
+  if (pool > 1) check_pool_mask(x, mask, y.numel());
   const DeviceGuard guard(x.device());
-  dm::conv_small_bwd(x.data_ptr(), w.data_ptr<float>(), dp.data_ptr(), yp.data_ptr(),
-                     pool > 1 ? (const uint8_t*)mask->data_ptr() : nullptr,
-                     dx.has_value() ? dx->data_ptr() : nullptr, dw.data_ptr<float>(),
-                     db.has_value() ? db->data_ptr<float>() : nullptr, work.data_ptr<float>(), B,
-                     Cin, H, W, Cout, K, (int)pad, (int)pool, relu ? 1 : 0, (float)beta, (int)bs,
-                     is_bf16(x), cur_stream());
+  const size_t lds = sizeof(float) * g.Cin * g.K * g.K;
+  TORCH_CHECK(lds <= dm::conv_small_lds_limit(), "conv_small_fwd: Cin ", g.Cin, " with K ", g.K,
+              " needs ", lds, " bytes of LDS, the launch has ", dm::conv_small_lds_limit());
+  dm::conv_small_fwd(x.data_ptr(), w.data_ptr<float>(),
+                     has(bias) ? bias->data_ptr<float>() : nullptr, y.data_ptr(),
+                     pool > 1 ? (uint8_t*)mask->data_ptr() : nullptr, g.B, g.Cin, g.H, g.W, g.Cout,
+                     g.K, (int)pad, (int)pool, relu ? 1 : 0, is_bf16(x), cur_stream());
 }
 
 int64_t conv_small_workspace(int64_t B, int64_t Cin, int64_t H, int64_t W, int64_t Cout,
                              int64_t K, int64_t pad, int64_t bs) {
+  TORCH_CHECK(bs >= 1, "bs must be >= 1, got ", bs);
   const long long OH = H + 2 * pad - K + 1, OW = W + 2 * pad - K + 1;
   const long long total = B * Cout * OH * OW;
   const long long S = (B + bs - 1) / bs;
   return (total + 63) / 64 * 64 + S * (Cout * Cin * K * K + Cout);
 }
 
+void conv_small_bwd(at::Tensor x, at::Tensor w, at::Tensor dp, at::Tensor yp,
+                    c10::optional<at::Tensor> mask, c10::optional<at::Tensor> dx, at::Tensor dw,
+                    c10::optional<at::Tensor> db, at::Tensor work, int64_t pad, int64_t pool,
+                    bool relu, double beta, int64_t bs) {
+  const SmallConvGeom g = small_conv_geom(x, w, pad, pool);
+  TORCH_CHECK(bs >= 1, "bs must be >= 1, got ", bs);
+  for (auto t : {std::make_pair(&dp, "dp"), std::make_pair(&yp, "yp")}) {
+    check_act(*t.first, t.second);
+    check_same_dev(x, *t.first, t.second);
+    TORCH_CHECK(is_bf16(*t.first) == is_bf16(x), t.second, " must have x's dtype");
+    check_shape4(*t.first, g.B, g.Cout, g.PH, g.PW, t.second);
+  }
+  check_same_dev(x, dw, "dw");
+  CHECK_F32(dw); CHECK_CONTIG(dw);
+  TORCH_CHECK(dw.sizes() == w.sizes(), "dw shape mismatch: expected ", w.sizes(), ", got ", dw.sizes());
+  if (has(db)) check_f32_vec(x, *db, g.Cout, "db");
+  if (has(dx)) {
+    check_act(*dx, "dx");
+    check_same_dev(x, *dx, "dx");
+    TORCH_CHECK(is_bf16(*dx) == is_bf16(x), "dx must have x's dtype");
+    TORCH_CHECK(dx->sizes() == x.sizes(), "dx shape mismatch: expected ", x.sizes(), ", got ", dx->sizes());
+  }
+  check_same_dev(x, work, "work");
+  CHECK_F32(work); CHECK_CONTIG(work);
+  const int64_t need = conv_small_workspace(g.B, g.Cin, g.H, g.W, g.Cout, g.K, pad, bs);
+  TORCH_CHECK(work.numel() >= need, "workspace too small: ", work.numel(), " < ", need);
+  if (pool > 1) check_pool_mask(x, mask, dp.numel());
+  const DeviceGuard guard(x.device());
+  if (has(dx)) {
+    // backward-data stages one image's padded upstream gradient in LDS: refuse an image that does
+    // not fit instead of a launch that fails and leaves dx unwritten
+    const size_t lds = dm::conv_small_bwd_data_lds(g.Cout, g.K, g.OH, g.OW);
+    TORCH_CHECK(lds <= dm::conv_small_lds_limit(), "conv_small_bwd: backward-data of a ", g.H,
+                " x ", g.W, " image (conv output ", g.OH, " x ", g.OW, ", Cout ", g.Cout, ", K ",
+                g.K, ") needs ", lds, " bytes of LDS, the launch has ", dm::conv_small_lds_limit());
+  }
+  dm::conv_small_bwd(x.data_ptr(), w.data_ptr<float>(), dp.data_ptr(), yp.data_ptr(),
+                     pool > 1 ? (const uint8_t*)mask->data_ptr() : nullptr,
+                     has(dx) ? dx->data_ptr() : nullptr, dw.data_ptr<float>(),
+                     has(db) ? db->data_ptr<float>() : nullptr, work.data_ptr<float>(), g.B,
+                     g.Cin, g.H, g.W, g.Cout, g.K, (int)pad, (int)pool, relu ? 1 : 0, (float)beta,
+                     (int)bs, is_bf16(x), cur_stream());
+}
+
 // ------------------------------------------------------------------ strided GEMM
+// (S, kchunk, chunks) of dm::gemm_plan: the split-K decision gemm() takes for a shape
+std::tuple<int64_t, int64_t, int64_t> gemm_plan(int64_t M, int64_t N, int64_t K, bool a_bf16,
+                                                bool lowp) {
+  TORCH_CHECK(M >= 0 && N >= 0 && K >= 1, "gemm_plan: M, N >= 0 and K >= 1");
+  const dm::GemmPlan p = dm::gemm_plan(M, N, K, a_bf16 ? 1 : 0, lowp ? 1 : 0);
+  return {p.S, p.kchunk, p.chunks};
+}
+
 // C[m,n] = alpha * sum_k A(m,k) B(k,n) + beta*C + bias ; strides in elements.
 void gemm(at::Tensor A, c10::optional<at::Tensor> Amask, at::Tensor B, c10::optional<at::Tensor> C,
           c10::optional<at::Tensor> C32, c10::optional<at::Tensor> bias, int64_t M, int64_t N,
           int64_t K, int64_t sam, int64_t sak, int64_t sbk, int64_t sbn, int64_t scm,
           double alpha, double beta, bool relu, bool lowp) {
-  TORCH_CHECK(A.is_cuda() && B.is_cuda());
+  TORCH_CHECK(A.is_cuda(), "A must be a HIP tensor");
+  check_same_dev(A, B, "B");
+  auto lowp_or_f32 = [](const at::Tensor& t, const char* n) {
+    TORCH_CHECK(t.scalar_type() == at::kFloat || t.scalar_type() == at::kBFloat16, n,
+                " must be fp32 or bf16, got ", t.scalar_type());
+  };
+  lowp_or_f32(A, "A");
+  lowp_or_f32(B, "B");
+  TORCH_CHECK(M >= 0 && N >= 0, "M and N must be >= 0, got ", M, ", ", N);
+  TORCH_CHECK(K >= 1, "K must be >= 1, got ", K);
+  TORCH_CHECK(M < (1LL << 31) && N < (1LL << 31) && K < (1LL << 31), "M, N, K must fit an int");
+  TORCH_CHECK(sam >= 0 && sak >= 0 && sbk >= 0 && sbn >= 0 && scm >= 0,
+              "strides must be non-negative");
   auto span_ok = [](const at::Tensor& t, int64_t r, int64_t c, int64_t sr, int64_t sc) {
-    return (r - 1) * sr + (c - 1) * sc < t.numel();
+    return r == 0 || c == 0 || (r - 1) * sr + (c - 1) * sc < t.numel();
   };
   TORCH_CHECK(span_ok(A, M, K, sam, sak), "A too small for M,K,strides");
   TORCH_CHECK(span_ok(B, K, N, sbk, sbn), "B too small for K,N,strides");
-  if (Amask.has_value()) TORCH_CHECK(Amask->scalar_type() == A.scalar_type() && Amask->numel() >= A.numel());
+  if (has(Amask)) {
+    check_same_dev(A, *Amask, "Amask");
+    TORCH_CHECK(Amask->scalar_type() == A.scalar_type(), "Amask must have A's dtype");
+    TORCH_CHECK(Amask->numel() >= A.numel(), "Amask must have at least A's ", A.numel(), " elements");
+  }
   void* cp = nullptr;
   int cbf = 0;
-  if (C.has_value()) { cp = C->data_ptr(); cbf = is_bf16(*C); TORCH_CHECK(span_ok(*C, M, N, scm, 1)); }
-  float* c32 = nullptr;
-  if (C32.has_value()) { CHECK_F32(*C32); c32 = C32->data_ptr<float>(); TORCH_CHECK(span_ok(*C32, M, N, scm, 1)); }
-  TORCH_CHECK(cp || c32, "an output is required");
-  if (bias.has_value()) { CHECK_F32(*bias); TORCH_CHECK(bias->numel() >= N); }
-  const DeviceGuard guard(A.device());
-  // bf16 path: split K over blocks when the output tile grid alone cannot fill the chip
-  // (the ResNet head: 64 output tiles), partial sums in an fp32 workspace reduced in order
-  int S = 1;
-  at::Tensor part;
-  if (lowp && is_bf16(A)) {
-    const long long tiles = ((M + 63) / 64) * ((N + 63) / 64);
-    while (S < 16 && tiles * S < 256 && K / (S * 2) >= 64) S *= 2;
-    if (S > 1) part = at::empty({(long long)S * M * N}, A.options().dtype(at::kFloat));
-  } else if (K >= 4 * 64) {
-    // fp32 kernel: its 64-deep LDS stages run serially per block, so a K of >= 4 stages on
-    // few output tiles is split over blocks (one or two stages each) + an ordered reduce
-    const long long tiles = ((M + 63) / 64) * ((N + 63) / 64);
-    while (S < 16 && tiles * S < 256 && K / (S * 2) >= 32) S *= 2;
-    if (S > 1) part = at::empty({(long long)S * M * N}, A.options().dtype(at::kFloat));
+  if (has(C)) {
+    check_same_dev(A, *C, "C");
+    lowp_or_f32(*C, "C");
+    cp = C->data_ptr(); cbf = is_bf16(*C);
+    TORCH_CHECK(span_ok(*C, M, N, scm, 1), "C too small for M,N,scm");
   }
+  float* c32 = nullptr;
+  if (has(C32)) {
+    check_same_dev(A, *C32, "C32");
+    CHECK_F32(*C32); c32 = C32->data_ptr<float>();
+    TORCH_CHECK(span_ok(*C32, M, N, scm, 1), "C32 too small for M,N,scm");
+  }
+  TORCH_CHECK(cp || c32, "an output is required");
+  if (has(bias)) {
+    check_same_dev(A, *bias, "bias");
+    CHECK_F32(*bias); TORCH_CHECK(bias->numel() >= N, "bias must have at least N elements");
+  }
+  if (M == 0 || N == 0) return;  // nothing to write (and no zero-sized grid)
+  const DeviceGuard guard(A.device());
+  const dm::GemmPlan plan = dm::gemm_plan(M, N, K, is_bf16(A), lowp ? 1 : 0);
+  at::Tensor part;
+  if (plan.S > 1) part = at::empty({(long long)plan.S * M * N}, A.options().dtype(at::kFloat));
   dm::gemm_strided(A.data_ptr(), optp(Amask), is_bf16(A), B.data_ptr(), is_bf16(B), cp, cbf, c32,
-                   bias.has_value() ? bias->data_ptr<float>() : nullptr, M, N, K, sam, sak, sbk,
+                   has(bias) ? bias->data_ptr<float>() : nullptr, M, N, K, sam, sak, sbk,
                    sbn, scm, (float)alpha, (float)beta, relu ? 1 : 0, lowp ? 1 : 0,
-                   S > 1 ? part.data_ptr<float>() : nullptr, S, cur_stream());
+                   plan.S > 1 ? part.data_ptr<float>() : nullptr, plan, cur_stream());
 }
 
 // ------------------------------------------------------------ CU-masked streams
@@ -394,9 +483,17 @@ void p2p_xgmi_recv(at::Tensor dst, int64_t ring, int64_t full, int64_t free_, in
 }
 
 void colsum(at::Tensor A, c10::optional<at::Tensor> Amask, at::Tensor out, double beta) {
-  TORCH_CHECK(A.is_cuda() && A.dim() == 2 && A.is_contiguous());
-  CHECK_F32(out);
-  TORCH_CHECK(out.numel() == A.size(1));
+  TORCH_CHECK(A.is_cuda() && A.dim() == 2 && A.is_contiguous(), "A must be a contiguous 2-d HIP tensor");
+  TORCH_CHECK(A.scalar_type() == at::kFloat || A.scalar_type() == at::kBFloat16,
+              "A must be fp32 or bf16, got ", A.scalar_type());
+  if (has(Amask)) {
+    check_same_dev(A, *Amask, "Amask");
+    TORCH_CHECK(Amask->scalar_type() == A.scalar_type(), "Amask must have A's dtype");
+    TORCH_CHECK(Amask->sizes() == A.sizes() && Amask->is_contiguous(),
+                "Amask must be contiguous with A's shape ", A.sizes(), ", got ", Amask->sizes());
+  }
+  check_f32_vec(A, out, A.size(1), "out");
+  if (A.size(1) == 0) return;
   const DeviceGuard guard(A.device());
   dm::colsum(A.data_ptr(), optp(Amask), is_bf16(A), out.data_ptr<float>(), A.size(0), A.size(1),
              (float)beta, cur_stream());
@@ -658,6 +755,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("sam"), py::arg("sak"),
         py::arg("sbk"), py::arg("sbn"), py::arg("scm"), py::arg("alpha"), py::arg("beta"),
         py::arg("relu"), py::arg("lowp") = false);
+  m.def("gemm_plan", &gemm_plan, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("a_bf16"),
+        py::arg("lowp"));
   m.def("colsum", &colsum);
   m.def("bias_act", &bias_act, py::arg("y"), py::arg("bias"), py::arg("out"), py::arg("relu"));
   m.def("cu_mask_stream", &cu_mask_stream);

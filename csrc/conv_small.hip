@@ -213,7 +213,8 @@ __global__ void __launch_bounds__(256) conv_small_bwd_w_kernel(
   }
 }
 
-// out[j] = beta*out[j] + sum_s part[s][j]   (fixed order → deterministic)
+// out[j] = beta*out[j] + sum_s part[s][j]   (fixed order → deterministic); beta == 0 overwrites:
+// a stale NaN/Inf in the gradient slot must not survive
 __global__ void __launch_bounds__(256) slab_reduce_kernel(const float* __restrict__ part,
                                                           int S, int n, float* __restrict__ outw,
                                                           int nw, float* __restrict__ outb,
@@ -223,13 +224,29 @@ __global__ void __launch_bounds__(256) slab_reduce_kernel(const float* __restric
   float s = 0.f;
   for (int i = 0; i < S; ++i) s += part[(long long)i * n + j];
   if (j < nw) {
-    outw[j] = beta * outw[j] + s;
+    outw[j] = beta != 0.f ? beta * outw[j] + s : s;
   } else if (outb) {
-    outb[j - nw] = beta * outb[j - nw] + s;
+    outb[j - nw] = beta != 0.f ? beta * outb[j - nw] + s : s;
   }
 }
 
 // ---------------------------------------------------------------- launchers
+size_t conv_small_bwd_data_lds(int Cout, int K, int OH, int OW) {
+  return sizeof(float) * ((size_t)Cout * K * K + (size_t)Cout * (OH + 2 * (K - 1)) * (OW + 2 * (K - 1)));
+}
+
+// the LDS one workgroup may have on the current device (the kernels here declare no static LDS
+// next to their dynamic array, so this is what a launch's dynamic request is held against)
+size_t conv_small_lds_limit() {
+  static int cached[64] = {};  // per device; queried once (every thread would store the same value)
+  int dev = 0, v = 0;
+  DM_CHECK(hipGetDevice(&dev));
+  if (dev >= 0 && dev < 64 && cached[dev] > 0) return (size_t)cached[dev];
+  DM_CHECK(hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+  if (dev >= 0 && dev < 64) cached[dev] = v;
+  return (size_t)v;
+}
+
 template <typename T>
 static void fwd_dispatch(const T* x, const float* w, const float* bias, T* y, uint8_t* mask,
                          int B, int Cin, int H, int W, int Cout, int K, int pad, int pool,
@@ -252,6 +269,7 @@ static void fwd_dispatch(const T* x, const float* w, const float* bias, T* y, ui
                                                           pad, relu, PH, PW);
   else
     abort();
+  DM_CHECK(hipGetLastError());
 }
 
 void conv_small_fwd(const void* x, const float* w, const float* bias, void* y, uint8_t* mask,
@@ -286,13 +304,15 @@ static void bwd_impl(const T* x, const float* w, const T* dp, const T* yp, const
   else
     unpool_relu_bwd_kernel<T, 1><<<grid_for(total, 256), 256, 0, st>>>(dp, yp, mask, dyc, total,
                                                                        OH, OW, PH, PW, relu);
+  DM_CHECK(hipGetLastError());
   if (dx) {
     dim3 g((H * W + 255) / 256, B * Cin);
-    const size_t sh = sizeof(float) * (Cout * K * K + Cout * (OH + 2 * (K - 1)) * (OW + 2 * (K - 1)));
+    const size_t sh = conv_small_bwd_data_lds(Cout, K, OH, OW);
     if (K == 5)
       conv_small_bwd_data_kernel<T, 5><<<g, 256, sh, st>>>(dyc, w, dx, Cin, H, W, Cout, OH, OW, pad);
     else
       conv_small_bwd_data_kernel<T, 3><<<g, 256, sh, st>>>(dyc, w, dx, Cin, H, W, Cout, OH, OW, pad);
+    DM_CHECK(hipGetLastError());
   }
   dim3 gw(Cout * Cin, S);
   if (K == 5)
@@ -301,7 +321,9 @@ static void bwd_impl(const T* x, const float* w, const T* dp, const T* yp, const
   else
     conv_small_bwd_w_kernel<T, 3><<<gw, 256, 0, st>>>(dyc, x, part, B, Cin, H, W, Cout, OH, OW,
                                                       pad, bs, nout);
+  DM_CHECK(hipGetLastError());
   slab_reduce_kernel<<<(nout + 255) / 256, 256, 0, st>>>(part, S, nout, dw, nw, db, beta);
+  DM_CHECK(hipGetLastError());
 }
 
 void conv_small_bwd(const void* x, const float* w, const void* dp, const void* yp,

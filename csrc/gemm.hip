@@ -16,6 +16,7 @@
 // LDS store; exact fp32 MFMA math either way).
 // Exact f32 numerics: the MFMA is a k-ordered fmaf chain (guide §3).
 #include "common.h"
+#include "kernels.h"
 
 namespace dm {
 
@@ -291,22 +292,44 @@ __global__ void __launch_bounds__(256) colsum_kernel(const T* __restrict__ A,
   if (rg == 0 && c < N) {
     const float t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] +
                     red[3][threadIdx.x];
-    out[c] = beta * out[c] + t;
+    out[c] = beta != 0.f ? beta * out[c] + t : t;  // beta == 0 overwrites (stale NaN/Inf)
   }
 }
 
 // ------------------------------------------------------------------ launchers
-// dtype codes: 0 = fp32, 1 = bf16
+// The split-K heuristic, in one place (the binding sizes `part` from it, the launcher below
+// takes the chunking from it).
+//   bf16 MFMA (lowp, bf16 A): split K over blocks when the output tile grid alone cannot fill
+//     the chip (the ResNet head: 64 output tiles); chunks of a multiple of 32, all S launched
+//     (a trailing chunk may be empty and then contributes zeros).
+//   fp32 MFMA: its 64-deep LDS stages run serially per block, so a K of >= 4 stages on few
+//     output tiles is split over blocks (one or two stages each); only non-empty chunks launch
+//     (LeNet fc1: 2 output tiles, K = 400 = 7 serial LDS stages -> 7 blocks of one stage each).
+GemmPlan gemm_plan(long long M, long long N, long long K, int a_bf16, int lowp) {
+  const long long tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
+  int S = 1;
+  if (lowp && a_bf16) {
+    while (S < 16 && tiles * S < 256 && K / (S * 2) >= 64) S *= 2;
+    if (S == 1) return {1, (int)K, 1};
+    return {S, (int)(((K + S - 1) / S + 31) / 32 * 32), S};
+  }
+  if (K >= 4 * FBK)
+    while (S < 16 && tiles * S < 256 && K / (S * 2) >= 32) S *= 2;
+  if (S == 1) return {1, (int)K, 1};
+  const int kchunk = (int)(((K + S - 1) / S + FBK - 1) / FBK * FBK);
+  return {S, kchunk, (int)((K + kchunk - 1) / kchunk)};
+}
+
+// dtype codes: 0 = fp32, 1 = bf16.  part: plan.S * M * N floats when plan.S > 1
 void gemm_strided(const void* A, const void* Amask, int a_bf16, const void* B, int b_bf16,
                   void* C, int c_bf16, float* C32, const float* bias, int M, int N, int K,
                   long long sam, long long sak, long long sbk, long long sbn, long long scm,
-                  float alpha, float beta, int relu, int lowp, float* part, int S,
-                  hipStream_t st) {
-  dim3 grid((N + GBN - 1) / GBN, (M + GBM - 1) / GBM);
+                  float alpha, float beta, int relu, int lowp, float* part,
+                  const GemmPlan& plan, hipStream_t st) {
+  dim3 grid((N + GBN - 1) / GBN, (M + GBM - 1) / GBM, plan.S > 1 ? plan.chunks : 1);
+  float* pp = plan.S > 1 ? part : nullptr;
+  const int kchunk = plan.kchunk;
   if (lowp && a_bf16) {  // bf16 MFMA (B rounded to bf16 while staging)
-    const int kchunk = S > 1 ? ((K + S - 1) / S + 31) / 32 * 32 : K;
-    if (S > 1) grid.z = S;
-    float* pp = S > 1 ? part : nullptr;
 #define DM_GEMM16(TB, TC)                                                                    \
   gemm_bf16mfma_kernel<TB, TC><<<grid, 256, 0, st>>>(                                        \
       (const bf16_t*)A, (const bf16_t*)Amask, (const TB*)B, (TC*)C, C32, bias, M, N, K, sam, \
@@ -316,36 +339,23 @@ void gemm_strided(const void* A, const void* Amask, int a_bf16, const void* B, i
     else if (c_bf16) DM_GEMM16(float, bf16_t);
     else DM_GEMM16(float, float);
 #undef DM_GEMM16
-    if (S > 1) {
-      const int g = grid_for((long long)M * N, 256, 2048);
-      if (c_bf16)
-        gemm_splitk_reduce_kernel<bf16_t><<<g, 256, 0, st>>>(part, S, M, N, (bf16_t*)C, C32, bias,
-                                                              scm, beta, relu);
-      else
-        gemm_splitk_reduce_kernel<float><<<g, 256, 0, st>>>(part, S, M, N, (float*)C, C32, bias,
-                                                             scm, beta, relu);
-    }
-    return;
-  }
-  // split-K for the fp32 kernel: the caller sized part for S chunks of K (LeNet fc1: 2
-  // output tiles, K = 400 = 7 serial LDS stages -> 7 blocks of one stage each + a reduce)
-  const int kchunk32 = S > 1 ? ((K + S - 1) / S + FBK - 1) / FBK * FBK : K;
-  float* pp32 = S > 1 ? part : nullptr;
-  if (S > 1) grid.z = (K + kchunk32 - 1) / kchunk32;
+  } else {
 #define DM_GEMM(TA, TB, TC)                                                                  \
   gemm_f32mfma_kernel<TA, TB, TC><<<grid, 256, 0, st>>>(                                     \
       (const TA*)A, (const TA*)Amask, (const TB*)B, (TC*)C, C32, bias, M, N, K, sam, sak, sbk, \
-      sbn, scm, alpha, beta, relu, pp32, kchunk32)
-  if (!a_bf16 && !b_bf16 && !c_bf16) DM_GEMM(float, float, float);
-  else if (!a_bf16 && !b_bf16 && c_bf16) DM_GEMM(float, float, bf16_t);
-  else if (a_bf16 && !b_bf16 && !c_bf16) DM_GEMM(bf16_t, float, float);
-  else if (a_bf16 && !b_bf16 && c_bf16) DM_GEMM(bf16_t, float, bf16_t);
-  else if (a_bf16 && b_bf16 && !c_bf16) DM_GEMM(bf16_t, bf16_t, float);
-  else if (a_bf16 && b_bf16 && c_bf16) DM_GEMM(bf16_t, bf16_t, bf16_t);
-  else if (!a_bf16 && b_bf16 && !c_bf16) DM_GEMM(float, bf16_t, float);
-  else DM_GEMM(float, bf16_t, bf16_t);
+      sbn, scm, alpha, beta, relu, pp, kchunk)
+    if (!a_bf16 && !b_bf16 && !c_bf16) DM_GEMM(float, float, float);
+    else if (!a_bf16 && !b_bf16 && c_bf16) DM_GEMM(float, float, bf16_t);
+    else if (a_bf16 && !b_bf16 && !c_bf16) DM_GEMM(bf16_t, float, float);
+    else if (a_bf16 && !b_bf16 && c_bf16) DM_GEMM(bf16_t, float, bf16_t);
+    else if (a_bf16 && b_bf16 && !c_bf16) DM_GEMM(bf16_t, bf16_t, float);
+    else if (a_bf16 && b_bf16 && c_bf16) DM_GEMM(bf16_t, bf16_t, bf16_t);
+    else if (!a_bf16 && b_bf16 && !c_bf16) DM_GEMM(float, bf16_t, float);
+    else DM_GEMM(float, bf16_t, bf16_t);
 #undef DM_GEMM
-  if (S > 1) {
+  }
+  DM_CHECK(hipGetLastError());
+  if (pp) {
     const int g = grid_for((long long)M * N, 256, 2048);
     if (c_bf16)
       gemm_splitk_reduce_kernel<bf16_t><<<g, 256, 0, st>>>(part, (int)grid.z, M, N, (bf16_t*)C,
@@ -353,6 +363,7 @@ void gemm_strided(const void* A, const void* Amask, int a_bf16, const void* B, i
     else
       gemm_splitk_reduce_kernel<float><<<g, 256, 0, st>>>(part, (int)grid.z, M, N, (float*)C, C32,
                                                            bias, scm, beta, relu);
+    DM_CHECK(hipGetLastError());
   }
 }
 
@@ -365,6 +376,7 @@ void colsum(const void* A, const void* Amask, int bf16, float* out, int M, int N
   else
     colsum_kernel<float><<<grid, 256, 0, st>>>((const float*)A, (const float*)Amask, out, M, N,
                                                beta);
+  DM_CHECK(hipGetLastError());
 }
 
 // out = act(y + bias) (fp32 -> fp32 or bf16): the tensor-parallel row-split head's epilogue,

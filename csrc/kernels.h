@@ -53,12 +53,19 @@ void conv_small_bwd(const void* x, const float* w, const void* dp, const void* y
                     const uint8_t* mask, void* dx, float* dw, float* db, float* work, int B,
                     int Cin, int H, int W, int Cout, int K, int pad, int pool, int relu,
                     float beta, int bs, bool bf16, hipStream_t st);
+// dynamic LDS the backward-data kernel asks for, and the most a launch on the current device gets
+size_t conv_small_bwd_data_lds(int Cout, int K, int OH, int OW);
+size_t conv_small_lds_limit();
 // gemm.hip
+// split-K decision of one GEMM shape: part holds S slabs of M*N floats, block z of `chunks`
+// reduces k in [z*kchunk, (z+1)*kchunk).  S == 1: no split (kchunk = K, chunks = 1)
+struct GemmPlan { int S, kchunk, chunks; };
+GemmPlan gemm_plan(long long M, long long N, long long K, int a_bf16, int lowp);
 void gemm_strided(const void* A, const void* Amask, int a_bf16, const void* B, int b_bf16,
                   void* C, int c_bf16, float* C32, const float* bias, int M, int N, int K,
                   long long sam, long long sak, long long sbk, long long sbn, long long scm,
-                  float alpha, float beta, int relu, int lowp, float* part, int S,
-                  hipStream_t st);
+                  float alpha, float beta, int relu, int lowp, float* part,
+                  const GemmPlan& plan, hipStream_t st);
 void bias_act(const float* y, const float* bias, void* out, int out_bf16, int M, int N, int relu,
               hipStream_t st);
 void colsum(const void* A, const void* Amask, int bf16, float* out, int M, int N, float beta,
