@@ -5,6 +5,9 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include <map>
+#include <mutex>
+
 #include "conv_cfg.h"
 #include "conv_geom.h"
 #include "kernels.h"
@@ -89,11 +92,74 @@ std::pair<const float*, const float*> pre_bn(const c10::optional<at::Tensor>& sc
   return {fp(*scale), fp(*shift)};
 }
 
+// The pipelined conv's balanced schedule (csrc/conv_pipe_plan.h) needs a workspace: one per
+// (device, stream), allocated zeroed at the first balanced launch on that stream and kept for
+// every later one, so that the side stream's launches never share the main stream's.  The
+// launcher asks for it through pipe_workspace() with the stream it launches on.
+struct PipeWs {
+  at::Tensor slots, words;  // [cap][256 x 256] fp32; [cap flags + timeout word (+ pad)] int32
+  unsigned seq = 0;
+  int cap = 0;
+};
+std::map<std::pair<int, hipStream_t>, PipeWs>& pipe_ws_map() {
+  static auto* m = new std::map<std::pair<int, hipStream_t>, PipeWs>();  // outlives torch's teardown
+  return *m;
+}
+std::mutex& pipe_ws_mutex() {
+  static std::mutex m;
+  return m;
+}
+dm::PipeWorkspace pipe_workspace(hipStream_t st, int cap) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || cap < 1) return {};
+  const std::lock_guard<std::mutex> lock(pipe_ws_mutex());
+  PipeWs& w = pipe_ws_map()[{dev, st}];
+  if (w.cap < cap) {
+    TORCH_CHECK(w.cap == 0, "pipe workspace: the CU count of a device does not change");
+    const auto dv = at::Device(at::kCUDA, (c10::DeviceIndex)dev);
+    w.slots = at::zeros({cap, 256 * 256}, at::TensorOptions().dtype(at::kFloat).device(dv));
+    w.words = at::zeros({(cap + 1 + 3) / 4 * 4}, at::TensorOptions().dtype(at::kInt).device(dv));
+    w.cap = cap;
+  }
+  if (++w.seq == 0) w.seq = 1;  // 0 is the untouched flag
+  unsigned* words = reinterpret_cast<unsigned*>(w.words.data_ptr<int>());
+  return {w.slots.data_ptr<float>(), words, words + w.cap, w.seq, w.cap};
+}
+
+// [(device, balanced launches so far, timeout word)] of every workspace (synchronises): the
+// tests' view of which schedule ran; raises like dmlab/parallel/xgmi.py's check() when a
+// workgroup gave up waiting for its neighbour's partial tile
+py::list conv_pipe_balance_state() {
+  py::list out;
+  const std::lock_guard<std::mutex> lock(pipe_ws_mutex());
+  for (auto& [key, w] : pipe_ws_map()) {
+    if (!w.cap) continue;
+    const int tmo = w.words[w.cap].item<int>();
+    TORCH_CHECK(!tmo, "conv_pipe: a workgroup of the balanced schedule timed out waiting for its "
+                      "neighbour's partial tile; that launch's output is incomplete");
+    out.append(py::make_tuple(key.first, (int64_t)w.seq, tmo));
+  }
+  return out;
+}
+
+// the `balance` argument of conv_fwd / conv_dgrad: "auto" (the launcher decides), "off" (the
+// data-parallel launch) or the workgroup count G of a forced balanced launch
+int pipe_sched(const py::object& balance) {
+  if (py::isinstance<py::str>(balance)) {
+    const auto v = balance.cast<std::string>();
+    TORCH_CHECK(v == "auto" || v == "off", "balance: \"auto\", \"off\" or a workgroup count");
+    return v == "auto" ? dm::kPipeAuto : 0;
+  }
+  const int G = balance.cast<int>();
+  TORCH_CHECK(G > 0, "balance: a workgroup count > 0");
+  return G;
+}
+
 // y = conv(x, w)  (+add) ; stats [T][2][Cout] optional
 void conv_fwd(at::Tensor x, at::Tensor wpack, at::Tensor y, c10::optional<at::Tensor> stats,
               c10::optional<at::Tensor> add, int64_t KH, int64_t KW, int64_t stride, int64_t pad,
               int64_t cfg, c10::optional<at::Tensor> pre_scale,
-              c10::optional<at::Tensor> pre_shift) {
+              c10::optional<at::Tensor> pre_shift, py::object balance) {
   // pre_scale/pre_shift: x is the previous conv's raw output and the conv consumes
   // relu(x*pre_scale + pre_shift) (fused BN-apply + ReLU; halo kernels only)
   need_bf16_nhwc(x, "x");
@@ -128,7 +194,7 @@ void conv_fwd(at::Tensor x, at::Tensor wpack, at::Tensor y, c10::optional<at::Te
     dm::conv_halo(bp(x), bp(wpack), bp(y), ap, sp, g, c->bn, c->halo_waves, cur_stream(), psc, psh);
     return;
   }
-  dm::igemm_fwd(bp(x), bp(wpack), bp(y), ap, sp, g, cfg, cur_stream());
+  dm::igemm_fwd(bp(x), bp(wpack), bp(y), ap, sp, g, cfg, cur_stream(), pipe_sched(balance));
 }
 
 // A data gradient as a forward-style GEMM: dy [N,OH,OW,Cout] is the input, dx [N,H,W,Cin] the
@@ -201,10 +267,10 @@ int64_t dgrad_s2_red_rows(int64_t N, int64_t H, int64_t W, int64_t cfg) {
 // tile's (blockIdx.z = class); false when cfg has neither for this geometry
 bool launch_s2(const bf* dy, const bf* wd, bf* dx, const dm::ConvGeomSet& set, int ng,
                const dm::ConvCfg& c, const bf* add, const dm::DgradSeg2* seg2,
-               const dm::BnBwdRed* red, hipStream_t st) {
+               const dm::BnBwdRed* red, hipStream_t st, int sched) {
   if (ng <= 0) return false;
   if (c.family == dm::ConvFamily::pipe &&
-      dm::conv_pipe_multi(dy, wd, dx, add, set, ng, c.id, st, seg2, red))
+      dm::conv_pipe_multi(dy, wd, dx, add, set, ng, c.id, st, seg2, red, sched))
     return true;
   return dm::igemm_fwd_multi(dy, wd, dx, add, nullptr, set, ng, c.id, st, seg2, red);
 }
@@ -217,7 +283,8 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
                 c10::optional<at::Tensor> red_scale, c10::optional<at::Tensor> red_shift,
                 c10::optional<at::Tensor> red_mean, c10::optional<at::Tensor> red_invstd,
                 c10::optional<at::Tensor> red_part, c10::optional<at::Tensor> red_mask,
-                c10::optional<at::Tensor> dy2, c10::optional<at::Tensor> wd2) {
+                c10::optional<at::Tensor> dy2, c10::optional<at::Tensor> wd2,
+                py::object balance) {
   // dy2 / wd2 (optional, stride 2): a 1x1/s2/p0 projection's output gradient and packed data-
   // gradient weights [Cin][1][1][C2]; its data gradient is merged into this launch (parity
   // class (0,0) gets a second K segment), so dx is written once, complete
@@ -239,6 +306,7 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
               "wd must be bf16 [Cin][KH][KW][Cout]");
   TORCH_CHECK(stride == 1 || stride == 2, "stride must be 1 or 2");
   const dm::ConvCfg& c = cfg_of(cfg);
+  const int sched = pipe_sched(balance);
   const bf* addp = nullptr;
   if (add.has_value()) { need_bf16_nhwc(*add, "add"); TORCH_CHECK(add->sizes() == dx.sizes()); addp = bp(*add); }
   const bool accumulate = addp != nullptr;
@@ -276,7 +344,7 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
                   "(csrc/conv_cfg.h red_s1), on a geometry its kernel covers");
       const dm::BnBwdRed red = red_in(conv_stats_rows(g.M, cfg));
       if (pipe)
-        dm::conv_pipe(bp(dy), bp(wd), bp(dx), addp, nullptr, g, c.id, st, &red);
+        dm::conv_pipe(bp(dy), bp(wd), bp(dx), addp, nullptr, g, c.id, st, &red, sched);
       else if (halo)
         dm::conv_halo(bp(dy), bp(wd), bp(dx), addp, nullptr, g, c.bn, c.halo_waves, st, nullptr,
                       nullptr, &red);
@@ -284,7 +352,7 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
         dm::conv_res64(bp(dy), bp(wd), bp(dx), addp, nullptr, g, st, nullptr, nullptr, &red);
       return;
     }
-    dm::igemm_fwd(bp(dy), bp(wd), bp(dx), addp, nullptr, g, cfg, st);
+    dm::igemm_fwd(bp(dy), bp(wd), bp(dx), addp, nullptr, g, cfg, st, sched);
     return;
   }
   dm::ConvGeomSet set{};
@@ -332,11 +400,11 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
   const bf* acc = accumulate ? bp(dx) : nullptr;
   const bool special = merged || red_y.has_value();
   if (launch_s2(bp(dy), bp(wd), bp(dx), set, ng, c, acc, merged ? &seg2 : nullptr,
-                red_y.has_value() ? &red : nullptr, st))
+                red_y.has_value() ? &red : nullptr, st, sched))
     return;
   TORCH_CHECK(!special, "merged / reducing stride-2 dgrad: unsupported cfg / geometry");
   for (int i = 0; i < ng; ++i)
-    dm::igemm_fwd(bp(dy), bp(wd), bp(dx), acc, nullptr, set.g[i], cfg, st);
+    dm::igemm_fwd(bp(dy), bp(wd), bp(dx), acc, nullptr, set.g[i], cfg, st, 0);
 }
 
 // dw (fp32 OIHW [Cout][Cin][KH][KW]) = beta*dw + Σ_m dy ⊗ im2col(x)
@@ -978,7 +1046,10 @@ py::object wgrad_cfg_info(int64_t cfg) { return cfg_dict(dm::wgrad_cfg((int)cfg)
 void register_resnet(pybind11::module_& m) {
   m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("wpack"), py::arg("y"), py::arg("stats"),
         py::arg("add"), py::arg("KH"), py::arg("KW"), py::arg("stride"), py::arg("pad"),
-        py::arg("cfg"), py::arg("pre_scale") = py::none(), py::arg("pre_shift") = py::none());
+        py::arg("cfg"), py::arg("pre_scale") = py::none(), py::arg("pre_shift") = py::none(),
+        py::arg("balance") = "auto");
+  dm::conv_pipe_set_workspace(&pipe_workspace);
+  m.def("conv_pipe_balance_state", &conv_pipe_balance_state);
   // ncols: unused; still accepted from the callers that pass it
   m.def("conv_stats_rows", [](int64_t M, int64_t cfg, int64_t) { return conv_stats_rows(M, cfg); },
         py::arg("M"), py::arg("cfg"), py::arg("ncols") = -1);
@@ -991,7 +1062,7 @@ void register_resnet(pybind11::module_& m) {
         py::arg("red_shift") = py::none(), py::arg("red_mean") = py::none(),
         py::arg("red_invstd") = py::none(), py::arg("red_part") = py::none(),
         py::arg("red_mask") = py::none(), py::arg("dy2") = py::none(),
-        py::arg("wd2") = py::none());
+        py::arg("wd2") = py::none(), py::arg("balance") = "auto");
   m.def("dgrad_s2_red_rows", &dgrad_s2_red_rows, py::arg("N"), py::arg("H"), py::arg("W"),
         py::arg("cfg"));
   m.def("conv_wgrad", &conv_wgrad, py::arg("x"), py::arg("dy"), py::arg("dw"), py::arg("slab"),

@@ -767,12 +767,12 @@ bool igemm_fwd_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t*
 // conv_cfg.h lists for cfg.  A geometry the specialised kernel does not cover runs on the row's
 // fallback igemm tile, which has the same row tile, so the statistics slab rows still match.
 void igemm_fwd(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-               const ConvGeom& g, int cfg, hipStream_t st) {
+               const ConvGeom& g, int cfg, hipStream_t st, int pipe_sched) {
   const ConvCfg* c = conv_cfg(cfg);
   if (!c) throw std::runtime_error("igemm_fwd: unknown cfg " + std::to_string(cfg));
   switch (c->family) {
     case ConvFamily::pipe:
-      if (conv_pipe_supported(g, cfg)) return conv_pipe(X, Wp, Y, ADD, stats, g, cfg, st);
+      if (conv_pipe_supported(g, cfg)) return conv_pipe(X, Wp, Y, ADD, stats, g, cfg, st, nullptr, pipe_sched);
       break;
     case ConvFamily::res64:
       return conv_res64(X, Wp, Y, ADD, stats, g, st);  // throws if unsupported

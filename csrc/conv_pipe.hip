@@ -32,6 +32,7 @@
 #include "common.h"
 #include "conv_cfg.h"
 #include "conv_geom.h"
+#include "conv_pipe_plan.h"
 #include "igemm_common.h"
 #include "kernels.h"
 
@@ -45,6 +46,7 @@ constexpr int PBM = 256;   // output pixels per tile
 constexpr int PBK = 64;    // K per step (one 128-B LDS row per tile row)
 constexpr unsigned POOB = 0x80000000u;
 typedef unsigned int u32x4_nt __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) unsigned gu32;  // the hand-off's words: global, never flat
 
 // BN output channels per tile (256 / 128 / 64); WM x WN waves, wave tile 256/WM x BN/WN;
 // MINW waves per SIMD the register budget is sized for.  (A PRE variant that applied the
@@ -57,15 +59,19 @@ typedef unsigned int u32x4_nt __attribute__((ext_vector_type(4)));
 // SEG2 (stride-2 data gradients): geometry s2.z (parity class (0,0)) runs C2/64 more K steps
 // over X2 / W2 at the row's own pixel -- the block's 1x1/s2 projection (conv_geom.h DgradSeg2;
 // here X2 has X's channel count, so the row's pixel base is shared)
-template <int BN, int WM, int WN, int MINW, bool RED = false, bool SEG2 = false>
-__global__ void __launch_bounds__(WM * WN * 64, MINW) conv_pipe_kernel(
+//
+// One tile (or, BAL, the K steps [k0, k1) of one) of geometry g = gs.g[gy]: M tile bx, N tile by,
+// part row prow.  BAL (the balanced schedule, conv_pipe_plan.h): acc_in, when set, holds the
+// fp32 accumulators of the steps [0, k0) and is loaded in place of the zeros; acc_out, when
+// set, receives the accumulators after step k1 - 1 in place of the epilogue and is published
+// through *flag = seq.  The MFMA chain of a split tile is the unsplit one's continued from the
+// same fp32 values, so every result is bit-identical to the data-parallel launch.
+template <int BN, int WM, int WN, bool RED, bool SEG2, bool BAL>
+__device__ __forceinline__ void pipe_tile(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, bf16_t* Y, const bf16_t* ADD,
-    float* __restrict__ stats, ConvGeomSet gs, unsigned xbytes, unsigned wbytes, int ntN,
-    int mtiles_max, int xcd, BnBwdRed red, DgradSeg2 s2) {
-  // blockIdx.y selects one of up to four geometries sharing X / W / Y (the parity classes of a
-  // stride-2 data gradient, which write disjoint output pixels); one geometry otherwise
-  const ConvGeom g = gs.g[blockIdx.y];
-  const int mtiles = (int)((g.M + PBM - 1) / PBM);
+    float* __restrict__ stats, const ConvGeom& g, const int gy, unsigned xbytes, unsigned wbytes,
+    const int bx, const int by, const long long prow, const BnBwdRed& red, const DgradSeg2& s2,
+    const int k0, const int k1, const float* acc_in, float* acc_out, unsigned* flag, unsigned seq) {
   constexpr int NW = WM * WN, NT = NW * 64;
   constexpr int TM = PBM / WM, TN = BN / WN;  // wave tile
   constexpr int RM = TM / 32, RN = TN / 32;   // 32x32 blocks per wave
@@ -76,35 +82,21 @@ __global__ void __launch_bounds__(WM * WN * 64, MINW) conv_pipe_kernel(
   constexpr unsigned STG = ABYTES + BN * PBK * 2;  // one pipeline stage
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
-  const int tid = threadIdx.x, lane = tid & 63;
+  int tid = threadIdx.x;
+  // BAL: the persistent loop must not keep this tile's per-thread set-up live through the
+  // previous tile's epilogue (hoisted out of the loop it costs spills), so it hangs on a value
+  // the compiler cannot see through
+  if constexpr (BAL) asm volatile("" : "+v"(tid));
+  const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid / WN, wn = wid % WN;
-
-  // block -> (M tile, N tile): the N tiles of one M tile are blocks b, b+8, ... (one XCD)
-  int bx = blockIdx.x, by = 0;
-  if (xcd) {
-    const int b = blockIdx.x, j = b >> 3;
-    by = j % ntN;
-    bx = (j / ntN) * 8 + (b & 7);
-  } else {
-    bx = blockIdx.x % mtiles_max;
-    by = blockIdx.x / mtiles_max;
-  }
-  // part row of this block (RED): parity classes of a multi-geometry launch stack their M tiles
-  const long long prow = (long long)blockIdx.y * mtiles_max + bx;
-  if (bx >= mtiles) {  // padding of the grid, or a smaller parity class
-    if constexpr (RED) {  // every part row is summed by the consumer
-      if (bx < mtiles_max && by == 0)
-        for (int c = threadIdx.x; c < 2 * g.Ncols; c += blockDim.x) red.part[prow * 2 * g.Ncols + c] = 0.f;
-    }
-    return;
-  }
   const int m0 = bx * PBM;
   const int n0 = by * BN;
   const int ntaps = g.nth * g.ntw;
   const int nchunk = g.C / PBK;
   const int S1 = ntaps * nchunk;
-  const int S = S1 + ((SEG2 && (int)blockIdx.y == s2.z) ? s2.C2 / PBK : 0);
+  // steps this call runs (BAL: of the tile's S, the range [k0, k1))
+  const int S = BAL ? k1 - k0 : S1 + ((SEG2 && gy == s2.z) ? s2.C2 / PBK : 0);
 
   const pi32x4 rsx = prsrc(X, xbytes);
   const pi32x4 rsw = prsrc(Wp, wbytes);
@@ -152,6 +144,14 @@ __global__ void __launch_bounds__(WM * WN * 64, MINW) conv_pipe_kernel(
   // offsets and advances the counters; one(q, st) issues DMA instruction q into stage st
   constexpr int ND = AI + BI;
   int icc = 0, ith = 0, itw = 0;
+  int ist = k0;  // BAL: the tile's step the next prep() is for; steps from k1 on load zeros
+  if constexpr (BAL) {
+    static_assert(!SEG2, "the balanced schedule has no merged segment");
+    icc = k0 / ntaps;
+    const int tp = k0 - icc * ntaps;
+    ith = tp / g.ntw;
+    itw = tp - ith * g.ntw;
+  }
   unsigned doff[ND];
   bool dseg = false;  // the prepared step reads the second segment
   auto prep = [&]() __attribute__((always_inline)) {
@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(WM * WN * 64, MINW) conv_pipe_kernel(
       // after the geometry's own steps (icc == nchunk), C2/64 steps of the projection: one
       // 64-channel chunk each, the row's own pixel (abase: X2 has X's channel count)
       const int c2 = icc - nchunk;
-      dseg = c2 >= 0 && c2 * PBK < s2.C2 && (int)blockIdx.y == s2.z;
+      dseg = c2 >= 0 && c2 * PBK < s2.C2 && gy == s2.z;
       if (dseg) {
         ++icc;
         const unsigned co = (unsigned)(c2 * PBK * 2);
@@ -180,7 +180,8 @@ __global__ void __launch_bounds__(WM * WN * 64, MINW) conv_pipe_kernel(
       }
     }
     const int dy = g.dy0 + th * g.dys, dx = g.dx0 + tw * g.dxs;
-    const bool live = cc < nchunk;  // steps past the end load zeros
+    bool live = cc < nchunk;  // steps past the end load zeros
+    if constexpr (BAL) live = ist++ < k1;
     const unsigned tapd = (unsigned)((dy * g.W + dx) * g.C * 2 + cc * PBK * 2);
     const unsigned wko =
         (unsigned)((((g.kh0 + th * g.khs) * g.KW + (g.kw0 + tw * g.kws)) * g.C + cc * PBK) * 2);
@@ -210,6 +211,22 @@ __global__ void __launch_bounds__(WM * WN * 64, MINW) conv_pipe_kernel(
     for (int j = 0; j < RN; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  if constexpr (BAL) {
+    // a slot holds float4 ((i RN + j) 4 + r / 4) of thread tid at [that index][tid]
+    if (acc_in) {
+      const float4* src = reinterpret_cast<const float4*>(acc_in) + tid;
+#pragma unroll
+      for (int i = 0; i < RM; ++i)
+#pragma unroll
+        for (int j = 0; j < RN; ++j)
+#pragma unroll
+          for (int r4 = 0; r4 < 4; ++r4) {
+            const float4 v = src[((i * RN + j) * 4 + r4) * NT];
+            acc[i][j][4 * r4 + 0] = v.x; acc[i][j][4 * r4 + 1] = v.y;
+            acc[i][j][4 * r4 + 2] = v.z; acc[i][j][4 * r4 + 3] = v.w;
+          }
+    }
+  }
 
   constexpr int NMF = RM * RN;  // MFMAs per 16-deep substep
   constexpr int NRD = RM + RN;  // fragment reads per substep
@@ -299,6 +316,30 @@ __global__ void __launch_bounds__(WM * WN * 64, MINW) conv_pipe_kernel(
   // ---- epilogue ----
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();  // every wave is done with the stage buffers (LDS reused below)
+  if constexpr (BAL) {
+    if (acc_out) {
+      // publish: write-through 16-byte stores, every wave drains its own, then one lane stores
+      // the flag (agent scope); the consumer polls it and acquires (pipe_wait)
+      const __amdgpu_buffer_rsrc_t rso =
+          __builtin_amdgcn_make_buffer_rsrc(acc_out, 0, PBM * BN * 4, 0x00020000);
+#pragma unroll
+      for (int i = 0; i < RM; ++i)
+#pragma unroll
+        for (int j = 0; j < RN; ++j)
+#pragma unroll
+          for (int r4 = 0; r4 < 4; ++r4) {
+            u32x4_nt v;
+            v[0] = __float_as_uint(acc[i][j][4 * r4 + 0]); v[1] = __float_as_uint(acc[i][j][4 * r4 + 1]);
+            v[2] = __float_as_uint(acc[i][j][4 * r4 + 2]); v[3] = __float_as_uint(acc[i][j][4 * r4 + 3]);
+            __builtin_amdgcn_raw_buffer_store_b128(
+                v, rso, (unsigned)((((i * RN + j) * 4 + r4) * NT + tid) * 16), 0, 16 /* sc1 */);
+          }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (tid == 0) __hip_atomic_store((gu32*)flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return;
+    }
+  }
   float* sred = reinterpret_cast<float*>(smem);  // [WM][BN][2] statistics partials
   if (stats) {
 #pragma unroll
@@ -467,10 +508,12 @@ __global__ void __launch_bounds__(WM * WN * 64, MINW) conv_pipe_kernel(
         for (int j = 0; j < 8; ++j) {
           const float yj = __uint_as_float((j & 1) ? (yw[j >> 1] & 0xffff0000u) : (yw[j >> 1] << 16));
           const float gj = __uint_as_float((j & 1) ? (ow[j >> 1] & 0xffff0000u) : (ow[j >> 1] << 16));
-          const bool pass = red.mask ? ((mb >> j) & 1u) != 0u : yj * rsc[j] + rsh[j] > 0.f;
+          // (explicit fmas: what the compiler contracts is not the same in every instantiation,
+          // and the balanced launch's part rows must equal the data-parallel launch's bit for bit)
+          const bool pass = red.mask ? ((mb >> j) & 1u) != 0u : __builtin_fmaf(yj, rsc[j], rsh[j]) > 0.f;
           const float dz = pass ? gj : 0.f;
           rs[j] += dz;
-          rq[j] += dz * (yj - rmu[j]);
+          rq[j] = __builtin_fmaf(dz, yj - rmu[j], rq[j]);
         }
       }
     }
@@ -507,12 +550,122 @@ __global__ void __launch_bounds__(WM * WN * 64, MINW) conv_pipe_kernel(
       }
     }
   }
+  // BAL: the next tile's DMA lands in LDS the other waves' epilogues may still be reading
+  if constexpr (BAL) __syncthreads();
+}
+
+// BN output channels per tile, WM x WN waves, MINW, RED, SEG2: see pipe_tile
+template <int BN, int WM, int WN, int MINW, bool RED = false, bool SEG2 = false>
+__global__ void __launch_bounds__(WM * WN * 64, MINW) conv_pipe_kernel(
+    const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, bf16_t* Y, const bf16_t* ADD,
+    float* __restrict__ stats, ConvGeomSet gs, unsigned xbytes, unsigned wbytes, int ntN,
+    int mtiles_max, int xcd, BnBwdRed red, DgradSeg2 s2) {
+  // blockIdx.y selects one of up to four geometries sharing X / W / Y (the parity classes of a
+  // stride-2 data gradient, which write disjoint output pixels); one geometry otherwise
+  const ConvGeom g = gs.g[blockIdx.y];
+  const int mtiles = (int)((g.M + PBM - 1) / PBM);
+  // block -> (M tile, N tile): the N tiles of one M tile are blocks b, b+8, ... (one XCD)
+  int bx = blockIdx.x, by = 0;
+  if (xcd) {
+    const int b = blockIdx.x, j = b >> 3;
+    by = j % ntN;
+    bx = (j / ntN) * 8 + (b & 7);
+  } else {
+    bx = blockIdx.x % mtiles_max;
+    by = blockIdx.x / mtiles_max;
+  }
+  // part row of this block (RED): parity classes of a multi-geometry launch stack their M tiles
+  const long long prow = (long long)blockIdx.y * mtiles_max + bx;
+  if (bx >= mtiles) {  // padding of the grid, or a smaller parity class
+    if constexpr (RED) {  // every part row is summed by the consumer
+      if (bx < mtiles_max && by == 0)
+        for (int c = threadIdx.x; c < 2 * g.Ncols; c += blockDim.x) red.part[prow * 2 * g.Ncols + c] = 0.f;
+    }
+    return;
+  }
+  pipe_tile<BN, WM, WN, RED, SEG2, false>(X, Wp, Y, ADD, stats, g, (int)blockIdx.y, xbytes, wbytes,
+                                          bx, by, prow, red, s2, 0, 0, nullptr, nullptr, nullptr, 0u);
+}
+
+constexpr unsigned long long PIPE_TIMEOUT_TICKS = 200000000ull;  // 2 s at 100 MHz
+
+// The consumer side of the hand-off: one lane polls the producer's flag relaxed until it
+// carries this launch's sequence number, then acquires once (agent scope) and the barrier lets
+// the other waves' plain loads follow.  The wait is bounded by wall time like comm_xgmi.hip's: on
+// a timeout *tmo is set and the caller leaves the tile alone (the host raises on that word).
+__device__ __forceinline__ bool pipe_wait(unsigned* flag, unsigned seq, unsigned* tmo) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int* ok = reinterpret_cast<int*>(smem);  // the stage buffers are idle between tiles
+  if (threadIdx.x == 0) {
+    int good = 1;
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    while (__hip_atomic_load((gu32*)flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != seq) {
+      __builtin_amdgcn_s_sleep(2);
+      if (__builtin_amdgcn_s_memrealtime() - t0 > PIPE_TIMEOUT_TICKS) {
+        __hip_atomic_store((gu32*)tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        good = 0;
+        break;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    *ok = good;
+  }
+  __syncthreads();
+  const bool r = *ok != 0;
+  __syncthreads();  // before the tile's DMA overwrites the word
+  return r;
+}
+
+// The balanced schedule (conv_pipe_plan.h): workgroup w runs the K steps pipe_range(T, S, G, w)
+// of the launch's T = mtiles x ntN tiles (N tile minor).  Order: (a) the head of the tile the
+// next workgroup finishes, published at once so that nobody waits long; (b) the whole tiles;
+// (c) the tail of the tile the previous workgroup started, continued from its slot.  Step (c)
+// waits only for step (a) of workgroup w - 1, which waits for nothing, and workgroups are
+// dispatched in order, so the launch needs no two workgroups resident together to finish.
+template <int BN, int WM, int WN, int MINW, bool RED>
+__global__ void __launch_bounds__(WM * WN * 64, MINW) conv_pipe_bal_kernel(
+    const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, bf16_t* Y, const bf16_t* ADD,
+    float* __restrict__ stats, ConvGeom g, unsigned xbytes, unsigned wbytes, int ntN, int S,
+    long long q, int r, float* slots, unsigned* flags, unsigned* tmo, unsigned seq, BnBwdRed red) {
+  const int w = blockIdx.x;
+  const long long b = w * q + (w < r ? w : r), e = b + q + (w < r ? 1 : 0);
+  const int tA = (int)(b / S), kA = (int)(b - (long long)tA * S);
+  const int tB = (int)(e / S), kB = (int)(e - (long long)tB * S);
+  constexpr size_t SLOT = (size_t)PBM * BN;  // floats
+  const DgradSeg2 s2{};
+  auto run = [&](int t, int k0, int k1, const float* in, float* out) __attribute__((always_inline)) {
+    const int bx = t / ntN, by = t - bx * ntN;
+    pipe_tile<BN, WM, WN, RED, false, true>(X, Wp, Y, ADD, stats, g, 0, xbytes, wbytes, bx, by, bx,
+                                            red, s2, k0, k1, in, out, flags + w, seq);
+  };
+  // one call site (one copy of the tile body): segment -1 is (a), tF .. tB - 1 are (b), tB is (c)
+  const int tF = tA + (kA > 0 ? 1 : 0);
+  for (int sg = kB > 0 ? tF - 1 : tF; sg <= (kA > 0 ? tB : tB - 1); ++sg) {
+    const bool head = sg < tF, tail = sg >= tB;
+    if (tail && !pipe_wait(flags + (w - 1), seq, tmo)) return;
+    run(head ? tB : tail ? tA : sg, tail ? kA : 0, head ? kB : S,
+        tail ? slots + (size_t)(w - 1) * SLOT : nullptr, head ? slots + (size_t)w * SLOT : nullptr);
+  }
+}
+
+PipeWorkspaceFn g_pipe_ws = nullptr;
+
+// workgroups resident at one per CU: the balanced grid never exceeds it
+int pipe_cu_count() {
+  static int cus[64] = {};
+  int dev = 0;
+  DM_CHECK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return 0;
+  if (!cus[dev])
+    DM_CHECK(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
+  return cus[dev];
 }
 
 template <int BN, int WM, int WN, int MINW>
 void launch_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
                  const ConvGeomSet& gs, int ng, hipStream_t st, const BnBwdRed* red = nullptr,
-                 const DgradSeg2* seg2 = nullptr) {
+                 const DgradSeg2* seg2 = nullptr, int sched = 0) {
   const ConvGeom& g = gs.g[0];
   constexpr size_t STG = (size_t)PBM * PBK * 2 + (size_t)BN * PBK * 2;
   const size_t sm_main = 2 * STG;
@@ -533,6 +686,33 @@ void launch_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD
   const BnBwdRed rarg = red ? *red : BnBwdRed{};
   const DgradSeg2 sarg = seg2 ? *seg2 : DgradSeg2{};
   constexpr int NT = WM * WN * 64;
+  // the balanced schedule (conv_pipe_plan.h; cfg 90's tile only): forced by sched > 0 wherever
+  // it is eligible, else when the model says it wins.  A capturing stream keeps the
+  // data-parallel launch: the sequence number is a kernel argument, frozen under replay
+  if constexpr (BN == 256 && WM == 2 && WN == 4 && MINW == 1) {
+    if (sched != 0 && g_pipe_ws) {
+      const int ncu = pipe_cu_count();
+      const int G = sched > 0 ? sched : ncu;
+      const long long T = (long long)mtiles * ntN;
+      const int S = g.nth * g.ntw * (g.C / PBK);
+      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+      if (G <= ncu && pipe_balanced_eligible(T, S, G, ng, seg2 != nullptr) &&
+          (sched > 0 || pipe_balanced_wins(T, S, G)) &&
+          hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
+        const PipeWorkspace ws = g_pipe_ws(st, ncu);
+        if (ws.slots && ws.cap >= G) {
+          auto kb = red ? conv_pipe_bal_kernel<BN, WM, WN, MINW, true>
+                        : conv_pipe_bal_kernel<BN, WM, WN, MINW, false>;
+          set_smem_attr(kb, sm);
+          kb<<<dim3((unsigned)G), NT, sm, st>>>(X, Wp, Y, ADD, stats, g, xb, wb, ntN, S, T * S / G,
+                                                (int)(T * S % G), ws.slots, ws.flags, ws.timeout,
+                                                ws.seq, rarg);
+          DM_CHECK(hipGetLastError());
+          return;
+        }
+      }
+    }
+  }
   set_smem_attr(k, sm);
   if (ntN > 1) {
     const unsigned mt8 = (unsigned)((mtiles + 7) / 8 * 8);
@@ -548,14 +728,16 @@ void launch_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD
 // launch_pipe on the tile of a pipe row of conv_cfg.h; false for any other cfg
 bool launch_pipe_cfg(int cfg, const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
                      float* stats, const ConvGeomSet& gs, int ng, hipStream_t st,
-                     const BnBwdRed* red, const DgradSeg2* seg2) {
+                     const BnBwdRed* red, const DgradSeg2* seg2, int sched) {
   return with_cfg_row<kConvCfgs, ConvFamily::pipe>(cfg, [&](auto row) {
     constexpr ConvCfg c = kConvCfgs[decltype(row)::value];
     static_assert(c.bm == PBM, "the pipe kernels' row tile");
-    launch_pipe<c.bn, c.wm, c.wn, c.minw>(X, Wp, Y, ADD, stats, gs, ng, st, red, seg2);
+    launch_pipe<c.bn, c.wm, c.wn, c.minw>(X, Wp, Y, ADD, stats, gs, ng, st, red, seg2, sched);
   });
 }
 }  // namespace
+
+void conv_pipe_set_workspace(PipeWorkspaceFn fn) { g_pipe_ws = fn; }
 
 bool conv_pipe_supported(const ConvGeom& g, int cfg) {
   const ConvCfg* c = conv_cfg(cfg);
@@ -568,20 +750,20 @@ bool conv_pipe_supported(const ConvGeom& g, int cfg) {
 }
 
 void conv_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-               const ConvGeom& g, int cfg, hipStream_t st, const BnBwdRed* red) {
-  if (!launch_pipe_cfg(cfg, X, Wp, Y, ADD, stats, ConvGeomSet::one(g), 1, st, red, nullptr))
+               const ConvGeom& g, int cfg, hipStream_t st, const BnBwdRed* red, int sched) {
+  if (!launch_pipe_cfg(cfg, X, Wp, Y, ADD, stats, ConvGeomSet::one(g), 1, st, red, nullptr, sched))
     throw std::runtime_error("conv_pipe: not a pipelined cfg");
 }
 
 // the parity classes of a stride-2 data gradient (no statistics) in one launch
 bool conv_pipe_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
                      const ConvGeomSet& gs, int ng, int cfg, hipStream_t st, const DgradSeg2* seg2,
-                     const BnBwdRed* red) {
+                     const BnBwdRed* red, int sched) {
   if (ng < 1 || ng > 4) return false;
   for (int i = 0; i < ng; ++i)
     if (!conv_pipe_supported(gs.g[i], cfg)) return false;
   if (seg2 && seg2->C2 != gs.g[0].C) return false;
-  return launch_pipe_cfg(cfg, X, Wp, Y, ADD, nullptr, gs, ng, st, red, seg2);
+  return launch_pipe_cfg(cfg, X, Wp, Y, ADD, nullptr, gs, ng, st, red, seg2, sched);
 }
 
 }  // namespace dm

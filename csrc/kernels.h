@@ -129,8 +129,9 @@ struct BnBwdRed;
 bool igemm_fwd_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
                      const ConvGeomSet& gs, int ng, int cfg, hipStream_t st,
                      const DgradSeg2* seg2 = nullptr, const BnBwdRed* red = nullptr);
+// pipe_sched: the pipelined tiles' schedule (conv_pipe's sched); the other kernels have none
 void igemm_fwd(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-               const ConvGeom& g, int cfg, hipStream_t st);
+               const ConvGeom& g, int cfg, hipStream_t st, int pipe_sched = -1);
 // conv_stem.hip: s2d stem (16 channels, 16 taps, 64 outputs) with resident weights (cfg 60)
 bool stem_conv_supported(const ConvGeom& g);
 void stem_conv(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, float* stats, const ConvGeom& g,
@@ -179,9 +180,27 @@ struct BnBwdRed {
 bool conv_pipe_supported(const ConvGeom& g, int cfg);
 bool conv_pipe_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
                      const ConvGeomSet& gs, int ng, int cfg, hipStream_t st,
-                     const DgradSeg2* seg2 = nullptr, const BnBwdRed* red = nullptr);
+                     const DgradSeg2* seg2 = nullptr, const BnBwdRed* red = nullptr,
+                     int sched = -1);
+// sched: kPipeAuto = the launcher decides (conv_pipe_plan.h), 0 = the data-parallel launch,
+// G > 0 = the balanced schedule on G workgroups wherever it is eligible (tests and A/B runs)
+constexpr int kPipeAuto = -1;
 void conv_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-               const ConvGeom& g, int cfg, hipStream_t st, const BnBwdRed* red = nullptr);
+               const ConvGeom& g, int cfg, hipStream_t st, const BnBwdRed* red = nullptr,
+               int sched = kPipeAuto);
+// The balanced schedule's workspace of one (device, stream), owned by the bindings: `cap` slots
+// of 256 x 256 fp32 accumulators, `cap` flag words and the timeout word, all zero at first; seq
+// is this launch's sequence number (a host counter per workspace, never 0), so that no word is
+// ever reset: a flag of an earlier launch cannot match.  Null slots = none (data-parallel).
+struct PipeWorkspace {
+  float* slots;
+  unsigned* flags;
+  unsigned* timeout;
+  unsigned seq;
+  int cap;
+};
+using PipeWorkspaceFn = PipeWorkspace (*)(hipStream_t st, int cap);
+void conv_pipe_set_workspace(PipeWorkspaceFn fn);
 // conv_res64.hip: persistent register-resident-weight 3x3 conv, 64 -> 64 channels (cfg 80);
 // statistics rows = res64_grid(M) (one per workgroup)
 bool conv_res64_supported(const ConvGeom& g);
