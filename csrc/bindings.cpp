@@ -128,6 +128,68 @@ void q8_decode_mean(at::Tensor gathered, at::Tensor out, double scale, int64_t m
                      cur_stream());
 }
 
+// ------------------------------------------------------------------ topk codec (csrc/gradk.hip)
+static void topk_check_keep(int64_t keep) {
+  TORCH_CHECK(keep >= 1 && keep <= dm::topk_max_keep(), "keep must be in 1..",
+              dm::topk_max_keep(), ", got ", keep);
+}
+
+int64_t topk_payload_bytes(int64_t n, int64_t keep) {
+  topk_check_keep(keep);
+  TORCH_CHECK(n >= 0, "n must be >= 0");
+  return (int64_t)dm::topk_payload_bytes(n, (int)keep);
+}
+
+void topk_encode(at::Tensor g, c10::optional<at::Tensor> r, at::Tensor payload, int64_t keep,
+                 int64_t max_blocks) {
+  topk_check_keep(keep);
+  CHECK_CUDA(g); CHECK_F32(g); CHECK_CONTIG(g);
+  CHECK_CUDA(payload); CHECK_CONTIG(payload);
+  TORCH_CHECK(payload.scalar_type() == at::kByte, "payload must be uint8");
+  TORCH_CHECK(g.dim() == 1 && payload.dim() == 1, "g and payload must be 1-d");
+  // one launch indexes bytes of the slice with 31 bits to spare: split a larger slice
+  TORCH_CHECK(g.numel() * 4 < (int64_t(1) << 31), "topk_encode: at most 2^29 - 1 elements per "
+              "call, got ", g.numel());
+  TORCH_CHECK(payload.numel() == dm::topk_payload_bytes(g.numel(), (int)keep),
+              "payload must hold topk_payload_bytes(n, keep) = ",
+              dm::topk_payload_bytes(g.numel(), (int)keep), " bytes, got ", payload.numel());
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(payload.data_ptr()) & 3) == 0,
+              "payload must be 4-B aligned");
+  TORCH_CHECK(g.device() == payload.device(), "g and payload on different devices");
+  float* rp = nullptr;
+  if (r.has_value() && r->defined()) {
+    CHECK_CUDA(*r); CHECK_F32(*r); CHECK_CONTIG(*r);
+    TORCH_CHECK(r->dim() == 1 && r->numel() == g.numel(), "residual size mismatch");
+    TORCH_CHECK(r->device() == g.device(), "g and residual on different devices");
+    rp = r->data_ptr<float>();
+  }
+  const DeviceGuard guard(g.device());
+  dm::topk_encode(g.data_ptr<float>(), rp, payload.data_ptr<uint8_t>(), g.numel(), (int)keep,
+                  (int)max_blocks, cur_stream());
+}
+
+void topk_decode_mean(at::Tensor gathered, at::Tensor out, int64_t keep, double scale,
+                      int64_t max_blocks) {
+  topk_check_keep(keep);
+  CHECK_CUDA(gathered); CHECK_CONTIG(gathered);
+  CHECK_CUDA(out); CHECK_F32(out); CHECK_CONTIG(out);
+  TORCH_CHECK(gathered.scalar_type() == at::kByte, "gathered must be uint8");
+  TORCH_CHECK(gathered.dim() == 2 && out.dim() == 1, "gathered must be [ws, payload], out 1-d");
+  TORCH_CHECK(gathered.size(0) >= 1 && gathered.size(0) <= INT32_MAX, "bad row count");
+  TORCH_CHECK(out.numel() * 4 < (int64_t(1) << 31), "topk_decode_mean: at most 2^29 - 1 "
+              "elements per call, got ", out.numel());
+  TORCH_CHECK(gathered.size(1) == dm::topk_payload_bytes(out.numel(), (int)keep),
+              "rows must hold topk_payload_bytes(n, keep) = ",
+              dm::topk_payload_bytes(out.numel(), (int)keep), " bytes, got ", gathered.size(1));
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(gathered.data_ptr()) & 3) == 0,
+              "gathered must be 4-B aligned");
+  TORCH_CHECK(gathered.device() == out.device(), "gathered and out on different devices");
+  const DeviceGuard guard(out.device());
+  dm::topk_decode_mean(gathered.data_ptr<uint8_t>(), gathered.size(1), (int)gathered.size(0),
+                       out.data_ptr<float>(), out.numel(), (int)keep, (float)scale,
+                       (int)max_blocks, cur_stream());
+}
+
 // ------------------------------------------------------------------ LARS (csrc/lars.hip)
 // Build the segment and chunk tables for tensors at `offsets` (elements, 16-B aligned) with
 // `numels` elements each inside a flat buffer of `total` elements.  Returns CPU int64 tensors
@@ -741,6 +803,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("g"), py::arg("r"), py::arg("payload"), py::arg("max_blocks") = 0);
   m.def("q8_decode_mean", &q8_decode_mean, "[ws, payload] -> scale * sum of decoded rows",
         py::arg("gathered"), py::arg("out"), py::arg("scale"), py::arg("max_blocks") = 0);
+  m.def("topk_payload_bytes", &topk_payload_bytes,
+        "bytes of one rank's topk payload for n gradient elements, keep entries per 2048-block",
+        py::arg("n"), py::arg("keep"));
+  m.def("topk_encode", &topk_encode,
+        "fp32 slice (+ residual) -> topk payload (fp32 values, uint16 in-block indices)",
+        py::arg("g"), py::arg("r"), py::arg("payload"), py::arg("keep"),
+        py::arg("max_blocks") = 0);
+  m.def("topk_decode_mean", &topk_decode_mean,
+        "[ws, payload] -> scale * sum over rows of the listed values, every element written",
+        py::arg("gathered"), py::arg("out"), py::arg("keep"), py::arg("scale"),
+        py::arg("max_blocks") = 0);
   m.def("lars_chunk", &dm::lars_chunk, "elements per LARS chunk (compile-time constant)");
   m.def("lars_table", &lars_table, "host-validated LARS segment/chunk tables (CPU int64)",
         py::arg("offsets"), py::arg("numels"), py::arg("adapted"), py::arg("total"));

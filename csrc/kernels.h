@@ -28,6 +28,20 @@ void q8_encode(const float* g, float* r, uint8_t* payload, long long n, int max_
 void q8_decode_mean(const uint8_t* gathered, long long row_bytes, int ws, float* out,
                     long long n, float scale, int max_blocks, hipStream_t st);
 
+// gradk.hip: "topk" block-wise gradient sparsification (blocks of 2048 from the slice's start,
+// the `keep` = 1..256 largest magnitudes of each).  payload = nb*keep fp32 values, nb*keep
+// uint16 in-block indices, padding to 16 bytes (topk_payload_bytes); r = nullptr: no error
+// feedback, otherwise r = 0 at the sent positions and g + r elsewhere.  gathered holds ws
+// payloads row_bytes apart; out = scale * sum over rows, in row order, of the listed values,
+// every element written.  max_blocks > 0 caps the grid.
+int topk_block();
+int topk_max_keep();
+long long topk_payload_bytes(long long n, int keep);
+void topk_encode(const float* g, float* r, uint8_t* payload, long long n, int keep,
+                 int max_blocks, hipStream_t st);
+void topk_decode_mean(const uint8_t* gathered, long long row_bytes, int ws, float* out,
+                      long long n, int keep, float scale, int max_blocks, hipStream_t st);
+
 // lars.hip: fused LARS step over the flat buffers (3 launches).  seg [n_tensors,5] and
 // chunks [n_chunks,3] are the int64 device tables described there; hyper holds
 // lars_hyper_count() floats (lr, momentum, weight decay, trust coefficient, eps,

@@ -237,7 +237,10 @@ class GradAggregator:
     the flat gradient buffer, averaging folded into its epilogue: GPU ranks of one node) |
     ``allgather_q8`` (block-wise int8 quantisation with error feedback,
     :mod:`dmlab.parallel.compress`: one encode, one all-gather of the ``uint8`` payload, one
-    decode-mean; ``error_feedback=False`` drops the residual; flat granularity only);
+    decode-mean; ``error_feedback=False`` drops the residual; flat granularity only) |
+    ``allgather_topk`` (block-wise top-k sparsification with error feedback through the same
+    encode / all-gather / decode-mean path; ``keep`` entries per 2048-element block; flat
+    granularity only);
     ``granularity``: ``flat`` (one coalesced collective) | ``per_param``.
     ``bytes_per_call``: the bytes this rank hands to the collectives per aggregation.
 
@@ -254,11 +257,19 @@ class GradAggregator:
     On the CPU (gloo) the collectives are synchronous and wall time is exact."""
 
     def __init__(self, model, method="allreduce", granularity="flat", timing=None,
-                 sync_timing=None, force=False, error_feedback=True):
+                 sync_timing=None, force=False, error_feedback=True, keep=32):
         self.model, self.method, self.granularity = model, method, granularity
         if method == "allgather_q8" and granularity != "flat":
             raise ValueError("allgather_q8 quantises blocks of the flat gradient buffer: "
                              "granularity must be 'flat', not %r" % (granularity,))
+        if method == "allgather_topk":
+            from .compress import _check_keep
+
+            if granularity != "flat":
+                raise ValueError("allgather_topk selects within blocks of the flat gradient "
+                                 "buffer: granularity must be 'flat', not %r" % (granularity,))
+            keep = _check_keep(keep)
+        self.keep = keep
         self.error_feedback = bool(error_feedback)
         self._q8 = None  # (compressor, payload, gathered), built at the first aggregation
         if timing is None:
@@ -293,7 +304,7 @@ class GradAggregator:
 
                 self._xgmi = XGMIAllReduce(cap=flat.grad.numel())
             self._xgmi(flat.grad, scale=1.0 / ws)
-        elif self.method == "allgather_q8":
+        elif self.method in ("allgather_q8", "allgather_topk"):
             self._aggregate_q8()
         else:
             raise ValueError(self.method)
@@ -313,10 +324,12 @@ class GradAggregator:
                 return
             buf = _flatten(gs)
         if self._q8 is None:
-            from .compress import Q8Compressor, payload_bytes
+            from .compress import make_compressor
 
-            nbytes = payload_bytes(buf.numel())
-            self._q8 = (Q8Compressor(buf.numel(), buf.device, self.error_feedback),
+            comp = make_compressor(self.method[len("allgather_"):], buf.numel(), buf.device,
+                                   self.error_feedback, self.keep)
+            nbytes = comp.payload_bytes(buf.numel())
+            self._q8 = (comp,
                         torch.zeros(nbytes, dtype=torch.uint8, device=buf.device),
                         torch.zeros((ws, nbytes), dtype=torch.uint8, device=buf.device))
         comp, payload, gathered = self._q8
@@ -328,14 +341,14 @@ class GradAggregator:
 
     @property
     def compressor(self):
-        """The q8 codec state (residual) once the first aggregation has built it."""
+        """The codec state (residual) once the first aggregation has built it."""
         return self._q8[0] if self._q8 is not None else None
 
     @property
     def bytes_per_call(self) -> int:
         """Bytes this rank hands to the collectives per aggregation: the flat gradient buffer
         (alignment padding included) for the coalesced methods, the parameters' own elements
-        for the per-tensor ones, the q8 payload for ``allgather_q8``."""
+        for the per-tensor ones, the payload for ``allgather_q8`` / ``allgather_topk``."""
         flat = _flat_of_model(self.model)
         per_tensor = self.granularity == "per_param" or self.method == "allgather_ref"
         if flat is not None and not per_tensor:
@@ -347,6 +360,10 @@ class GradAggregator:
             from .compress import payload_bytes
 
             return payload_bytes(n)
+        if self.method == "allgather_topk":
+            from .compress import topk_payload_bytes
+
+            return topk_payload_bytes(n, self.keep)
         return n * el
 
     def __call__(self):

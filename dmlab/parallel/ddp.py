@@ -32,6 +32,10 @@ task3/dist_utils.py:40-46).  Here:
   bucket's gradient slice on the main stream (about 1/3.94 of the fp32 bytes sent; every rank
   decodes the same bits).  All buffers are allocated at construction.  Runs on the Python
   bucket state machine; not combinable with ``comm_dtype`` or ``small_allreduce="xgmi"``.
+* Optional top-k gradient sparsification with error feedback (``compress="topk"``,
+  ``compress_keep=K``): the same bucket path with the other codec of that module.  Every
+  2048-element block of a bucket sends its K largest entries of gradient + residual as
+  (fp32 value, uint16 index) and carries the rest forward (K = 32: 1/42.7 of the fp32 bytes).
 * Bucket hooks on the weight-gradient side stream (``side_stream_hooks``; default on with
   RCCL buckets, off with ``small_allreduce="xgmi"`` whose spinning kernel would block the
   side stream; ``DMLAB_DDP_SIDE_HOOKS=0/1`` forces either).  Off = the one-layer-lag scheme
@@ -79,7 +83,7 @@ from .comm import avg_supported, init_parameters
 
 
 class _Bucket:
-    __slots__ = ("lo", "hi", "params", "pending", "work", "comm_buf", "scaled", "q8")
+    __slots__ = ("lo", "hi", "params", "pending", "work", "comm_buf", "scaled", "cmp")
 
     def __init__(self, lo, hi, params):
         self.lo, self.hi, self.params = lo, hi, params
@@ -87,7 +91,7 @@ class _Bucket:
         self.work = None
         self.comm_buf = None
         self.scaled = False
-        self.q8 = None  # compress="q8": (this rank's payload slice, [ws, bytes] gather slice)
+        self.cmp = None  # compress=...: (this rank's payload slice, [ws, bytes] gather slice)
 
 
 
@@ -100,19 +104,26 @@ class DistributedDataParallel(nn.Module):
                  small_cap_mb: float = 4.0, native: bool | None = None, xgmi_algo: str = "auto",
                  side_stream_hooks: bool | None = None, broadcast_buffers: bool = True,
                  buffer_sync_every: int = 1, force_comm: bool | None = None,
-                 compress: str | None = None, error_feedback: bool = True):
+                 compress: str | None = None, error_feedback: bool = True,
+                 compress_keep: int = 32):
         super().__init__()
-        if compress not in (None, "q8"):
-            raise ValueError("compress: None | 'q8'")
+        if compress not in (None, "q8", "topk"):
+            raise ValueError("compress: None | 'q8' | 'topk'")
         if compress is not None and comm_dtype is not None:
-            raise ValueError("compress='q8' sends int8 codes: it cannot be combined with comm_dtype")
+            raise ValueError(f"compress={compress!r} sends its own payload format: it cannot be "
+                             "combined with comm_dtype")
         if compress is not None and small_allreduce == "xgmi":
-            raise ValueError("compress='q8' all-gathers its payload: it cannot be combined with "
-                             "small_allreduce='xgmi'")
+            raise ValueError(f"compress={compress!r} all-gathers its payload: it cannot be "
+                             "combined with small_allreduce='xgmi'")
+        if compress == "topk":
+            from .compress import _check_keep
+
+            compress_keep = _check_keep(compress_keep)
         self.compress = compress
-        self.compressor = None     # Q8Compressor (owns the error-feedback residual)
-        self._q8_payload = None    # this rank's payloads, bucket after bucket
-        self._q8_gathered = None   # every rank's payloads: per bucket one [ws, bytes] block
+        self.compress_keep = compress_keep
+        self.compressor = None      # Q8Compressor / TopKCompressor (owns the residual)
+        self._cmp_payload = None    # this rank's payloads, bucket after bucket
+        self._cmp_gathered = None   # every rank's payloads: per bucket one [ws, bytes] block
         self.module = module
         self.ws = env.get_world_size()
         if force_comm is None:
@@ -186,7 +197,7 @@ class DistributedDataParallel(nn.Module):
             # the compressed exchange runs on the Python bucket state machine below
             native = False
             if self.comm_active:
-                self._setup_q8(error_feedback)
+                self._setup_compress(error_feedback)
         if native is None:
             native = self.comm_active and _native_reducer_available()
         # persistent communication buffer of the low-precision gradient copy (no per-step
@@ -199,32 +210,33 @@ class DistributedDataParallel(nn.Module):
         if native and self.comm_active:
             self._build_native(small_cap_mb)
 
-    # ------------------------------------------------------------------ q8 compression
-    def _setup_q8(self, error_feedback):
+    # ------------------------------------------------------------------ compression
+    def _setup_compress(self, error_feedback):
         """Every buffer of the compressed exchange, allocated once (a step allocates nothing,
         so it can be captured): the residual, this rank's payloads laid end to end, and per
         bucket one contiguous ``[ws, payload_bytes]`` block for the gathered payloads."""
-        from .compress import Q8Compressor, payload_bytes
+        from .compress import make_compressor
 
         if self.grad_buf.dtype != torch.float32:
-            raise ValueError("compress='q8' needs fp32 gradients")
+            raise ValueError(f"compress={self.compress!r} needs fp32 gradients")
         dev = self.grad_buf.device
-        self.compressor = Q8Compressor(self.grad_buf.numel(), dev, error_feedback)
-        sizes = [payload_bytes(b.hi - b.lo) for b in self.buckets]
+        self.compressor = make_compressor(self.compress, self.grad_buf.numel(), dev,
+                                          error_feedback, self.compress_keep)
+        sizes = [self.compressor.payload_bytes(b.hi - b.lo) for b in self.buckets]
         total = sum(sizes)
-        self._q8_payload = torch.zeros(total, dtype=torch.uint8, device=dev)
-        self._q8_gathered = torch.zeros(self.ws * total, dtype=torch.uint8, device=dev)
+        self._cmp_payload = torch.zeros(total, dtype=torch.uint8, device=dev)
+        self._cmp_gathered = torch.zeros(self.ws * total, dtype=torch.uint8, device=dev)
         off = 0
         for b, nb in zip(self.buckets, sizes):
-            b.q8 = (self._q8_payload[off:off + nb],
-                    self._q8_gathered[self.ws * off:self.ws * (off + nb)].view(self.ws, nb))
+            b.cmp = (self._cmp_payload[off:off + nb],
+                     self._cmp_gathered[self.ws * off:self.ws * (off + nb)].view(self.ws, nb))
             off += nb
 
-    def _launch_q8(self, b: _Bucket):
+    def _launch_compressed(self, b: _Bucket):
         """Encode on the current stream (the weight-gradient side stream under
         ``side_stream_hooks``), then gather every rank's payload asynchronously.  Always the
         asynchronous form: a compressed bucket never takes the main-stream tail branch."""
-        payload, gathered = b.q8
+        payload, gathered = b.cmp
         self.compressor.encode(self.grad_buf[b.lo:b.hi], b.lo, payload)
         if dist.get_backend(self.pg) == "nccl":
             b.work = dist.all_gather_into_tensor(gathered, payload, group=self.pg, async_op=True)
@@ -237,8 +249,8 @@ class DistributedDataParallel(nn.Module):
     def comm_bytes_per_step(self) -> int:
         """Bytes this rank hands to the bucket collectives per step."""
         n = sum(b.hi - b.lo for b in self.buckets)
-        if self._q8_payload is not None:
-            return self._q8_payload.numel()
+        if self._cmp_payload is not None:
+            return self._cmp_payload.numel()
         if self._comm_flat is not None:
             return n * self._comm_flat.element_size()
         return n * self.grad_buf.element_size()
@@ -447,8 +459,8 @@ class DistributedDataParallel(nn.Module):
         if b.work is not None or not self.comm_active:
             b.work = b.work or True
             return
-        if b.q8 is not None:
-            self._launch_q8(b)
+        if b.cmp is not None:
+            self._launch_compressed(b)
             return
         view = self.grad_buf[b.lo:b.hi]
         if self._xgmi is not None and self.comm_dtype is None and view.numel() <= self._xgmi.cap:
@@ -558,10 +570,10 @@ class DistributedDataParallel(nn.Module):
             if b.work is not None and b.work is not True:
                 b.work.wait()
             view = self.grad_buf[b.lo:b.hi]
-            if b.q8 is not None and b.work is not None:
+            if b.cmp is not None and b.work is not None:
                 # decode every rank's payload into the gradient slice, in rank order
                 c = 1.0 / self.ws if (self.average and not self._fold) else 1.0
-                self.compressor.decode_mean(b.q8[1], view, c)
+                self.compressor.decode_mean(b.cmp[1], view, c)
                 b.scaled = True
             if b.comm_buf is not None:
                 view.copy_(b.comm_buf)

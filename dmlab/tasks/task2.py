@@ -10,8 +10,10 @@ Launch any of:
     torchrun --nproc-per-node 2 -m dmlab.tasks.task2 --aggregation allgather
     python -m dmlab.tasks.task2 --n_devices 2 --rank 0   (and --rank 1; reference CLI)
     python -m dmlab.tasks.task2 --n_devices 2 --spawn    (model-mp.py behaviour)
-Options: ``--aggregation {allreduce,allgather,allgather_ref,allreduce_xgmi,allgather_q8}``
-(``allgather_q8``: int8 quantisation with error feedback, ``--no-error-feedback`` drops it),
+Options: ``--aggregation {allreduce,allgather,allgather_ref,allreduce_xgmi,allgather_q8,
+allgather_topk}`` (``allgather_q8``: int8 quantisation with error feedback;
+``allgather_topk``: the ``--compress-keep K`` largest entries of every 2048-element block with
+error feedback; ``--no-error-feedback`` drops the residual of either),
 ``--granularity {flat,per_param}``, ``--straggler-rank R --straggler-delay-ms D
 [--straggler-mode host|device]``.
 """
@@ -48,12 +50,17 @@ def parse_args(argv=None):
     p.add_argument("--momentum", type=float, default=0.9)
     p.add_argument("--aggregation", default="allreduce",
                    choices=["allreduce", "allgather", "allgather_ref", "allreduce_xgmi",
-                            "allgather_q8"],
+                            "allgather_q8", "allgather_topk"],
                    help="allreduce_xgmi: the one-shot xGMI peer-memory kernel over the flat "
                         "gradient buffer (GPU ranks of one node); allgather_q8: block-wise "
-                        "int8 quantisation with error feedback, all-gathered and averaged")
+                        "int8 quantisation with error feedback, all-gathered and averaged; "
+                        "allgather_topk: the --compress-keep largest entries of every "
+                        "2048-element block as (value, index) pairs, with error feedback")
     p.add_argument("--no-error-feedback", action="store_true",
-                   help="allgather_q8: do not carry the quantisation error to the next step")
+                   help="allgather_q8 / allgather_topk: do not carry the compression error to "
+                        "the next step")
+    p.add_argument("--compress-keep", type=int, default=32, metavar="K",
+                   help="allgather_topk: entries kept per 2048-element block (1..256)")
     p.add_argument("--force-comm", action="store_true",
                    help="at one rank with a process group (--backend nccl): run the collectives "
                         "anyway, to measure the device communication path on a single GPU")
@@ -82,19 +89,24 @@ def run(a):
     loader = DeviceLoader(train_set.to(dev), a.batch_size, sampler=sampler)
     opt = SGD(model.parameters(), lr=a.lr, momentum=a.momentum)
     comm.init_parameters(model)                       # task2/model.py:46
-    if a.no_error_feedback and a.aggregation != "allgather_q8":
-        raise SystemExit("--no-error-feedback belongs to --aggregation allgather_q8")
+    if a.no_error_feedback and a.aggregation not in ("allgather_q8", "allgather_topk"):
+        raise SystemExit("--no-error-feedback belongs to --aggregation allgather_q8 or "
+                         "allgather_topk")
+    if a.compress_keep != 32 and a.aggregation != "allgather_topk":
+        raise SystemExit("--compress-keep belongs to --aggregation allgather_topk")
     try:
         agg = comm.GradAggregator(model, a.aggregation, a.granularity, force=a.force_comm,
-                                  error_feedback=not a.no_error_feedback)
+                                  error_feedback=not a.no_error_feedback, keep=a.compress_keep)
     except ValueError as e:
         raise SystemExit(f"--aggregation {a.aggregation}: {e}")
     strag = Straggler(a.straggler_rank, a.straggler_delay_ms, a.straggler_mode)
     stats = train(model, loader, CrossEntropyLoss(), opt, a.epochs, rank=rank, aggregate=agg,
                   straggler=strag, batch_size=a.batch_size, max_steps=a.max_steps)
     print("Training time: {}".format(stats["train_time"]))
-    print(f"Total communication time: {agg.comm_time}")
-    print(f"Communication bytes per step: {agg.bytes_per_call}")
+    # one write for the two lines: every rank prints them, and with unbuffered output separate
+    # prints (and a print's own trailing newline) interleave with the other ranks' lines
+    print(f"Total communication time: {agg.comm_time}\n"
+          f"Communication bytes per step: {agg.bytes_per_call}\n", end="")
     if not a.no_test and rank == 0:
         stats["accuracy"] = test(model, DeviceLoader(test_set.to(dev), 32))
     stats.update(rank=rank, world_size=ws, aggregation=a.aggregation, granularity=a.granularity,

@@ -88,11 +88,16 @@ def parse_args(argv=None):
                         "world size > 1 on GPUs a startup self-check runs one xGMI call against "
                         "RCCL (exact); auto/xgmi use the kernel for LeNet only if it passes on "
                         "every rank (RCCL otherwise); ResNet-18 stays on RCCL under auto")
-    p.add_argument("--compress", default="none", choices=["none", "q8"],
+    p.add_argument("--compress", default="none", choices=["none", "q8", "topk"],
                    help="q8: DDP exchanges block-wise int8 gradients with error feedback "
-                        "(all-gather + decode-mean) instead of all-reducing fp32")
+                        "(all-gather + decode-mean) instead of all-reducing fp32; topk: the "
+                        "--compress-keep largest entries of every 2048-element block as "
+                        "(value, index) pairs, with error feedback, on the same path")
     p.add_argument("--no-error-feedback", action="store_true",
-                   help="--compress q8: do not carry the quantisation error to the next step")
+                   help="--compress q8 / topk: do not carry the compression error to the next "
+                        "step")
+    p.add_argument("--compress-keep", type=int, default=32, metavar="K",
+                   help="--compress topk: entries kept per 2048-element block (1..256)")
     p.add_argument("--data", default="./data")
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--train-samples", type=int, default=None)
@@ -139,11 +144,16 @@ def main(argv=None):
     if a.topk < 0:
         raise SystemExit("--topk must be >= 0")
     if a.compress != "none" and a.dp != "ddp":
-        raise SystemExit("--compress q8 runs inside DDP's buckets: it needs --dp ddp")
+        raise SystemExit(f"--compress {a.compress} runs inside DDP's buckets: it needs --dp ddp")
     if a.compress != "none" and a.allreduce == "xgmi":
-        raise SystemExit("--compress q8 all-gathers its payload: not with --allreduce xgmi")
+        raise SystemExit(f"--compress {a.compress} all-gathers its payload: not with "
+                         "--allreduce xgmi")
     if a.no_error_feedback and a.compress == "none":
-        raise SystemExit("--no-error-feedback belongs to --compress q8")
+        raise SystemExit("--no-error-feedback belongs to --compress q8 or topk")
+    if a.compress != "topk" and a.compress_keep != 32:
+        raise SystemExit("--compress-keep belongs to --compress topk")
+    if not 1 <= a.compress_keep <= 256:
+        raise SystemExit("--compress-keep must be in 1..256")
     if a.fused == "1" and a.augment != "none":
         raise SystemExit("--fused 1 reads the dataset rows inside the fused LeNet step; "
                          "--augment needs the layer-wise loop (--fused auto or 0)")
@@ -232,13 +242,25 @@ def main(argv=None):
         net = DDP(model, bucket_cap_mb=a.bucket_mb,  # broadcasts rank-0 params
                   small_allreduce="xgmi" if a.allreduce == "xgmi" and dev.type == "cuda" else None,
                   compress=None if a.compress == "none" else a.compress,
-                  error_feedback=not a.no_error_feedback)
+                  error_feedback=not a.no_error_feedback, compress_keep=a.compress_keep)
         net.fold_average_into(opt)
-        if resumed.get("q8_residual") is not None and net.compressor is not None:
+        if resumed.get("q8_residual") is not None and net.compressor is not None \
+                and a.compress == "q8":
             # the residual is per-rank training state; it only fits the same world size
             if not net.load_residual_state(resumed["q8_residual"]) and rank == 0:
                 print("checkpoint: q8 residual not restored (world size, buffer size or "
                       "--no-error-feedback differs); starting from a zero residual")
+        elif resumed.get("topk_residual") is not None and net.compressor is not None \
+                and a.compress == "topk":
+            if not net.load_residual_state(resumed["topk_residual"]) and rank == 0:
+                print("checkpoint: topk residual not restored (world size, buffer size or "
+                      "--no-error-feedback differs); starting from a zero residual")
+        elif net.compressor is not None and rank == 0:
+            other = {"q8": "topk_residual", "topk": "q8_residual"}[a.compress]
+            if resumed.get(other) is not None:
+                print(f"checkpoint: its {other.split('_')[0]} residual belongs to the other "
+                      f"codec and is not restored; --compress {a.compress} starts from a zero "
+                      "residual")
         agg = None
     else:
         comm.init_parameters(model)
@@ -289,7 +311,7 @@ def main(argv=None):
 
         extra = {}
         if a.compress != "none":  # every rank's residual (a collective), kept by rank 0
-            extra["q8_residual"] = net.residual_state()
+            extra[f"{a.compress}_residual"] = net.residual_state()
         checkpoint.save(a.save, model, opt, epochs=a.epochs, **extra)
     sharded = a.eval == "sharded"
     ev_kw = {}
