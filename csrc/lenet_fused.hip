@@ -219,10 +219,14 @@ __global__ void __launch_bounds__(LT) lenet_sample_kernel(
     const float mx = wave_max(z);
     const float e = lane < 10 ? __expf(z - mx) : 0.f;
     const float se = wave_sum(e);
-    const int lab = (int)labels[row];
+    // a label outside [0, 10) (tested as 64-bit) is ignored as in ce_fwd_bwd_kernel: row loss
+    // 0 and a zero seed, so the row adds nothing to any gradient; the mean still divides by B
+    const long long lab64 = labels[row];
+    const bool valid = lab64 >= 0 && lab64 < 10;
+    const int lab = valid ? (int)lab64 : 0;
     const float zl = __shfl(z, lab, 64);
-    if (lane < 10) dl[lane] = (e / se - (lane == lab ? 1.f : 0.f)) * inv_b;
-    if (lane == 0) rowloss[b] = mx + __logf(se) - zl;
+    if (lane < 10) dl[lane] = valid ? (e / se - (lane == lab ? 1.f : 0.f)) * inv_b : 0.f;
+    if (lane == 0) rowloss[b] = valid ? mx + __logf(se) - zl : 0.f;
   }
   __syncthreads();
   probe_stamp<PROBE>(probe, b, tid, 6);
