@@ -72,12 +72,20 @@ int64_t conv_stats_rows(int64_t M, int64_t cfg) {
   return bm ? (M + bm - 1) / bm : dm::res64_grid(M);
 }
 
+bool is_u8(const at::Tensor& t) {
+  return t.is_cuda() && t.scalar_type() == at::kByte && t.is_contiguous();
+}
+
 // A 1-bit mask over the elements of `of` (bit j of byte i = element 8i + j), or null
 const unsigned char* bit_mask(const c10::optional<at::Tensor>& m, const at::Tensor& of,
                               const char* n) {
   if (!m.has_value()) return nullptr;
-  TORCH_CHECK(m->is_cuda() && m->scalar_type() == at::kByte && m->is_contiguous() &&
-                  m->numel() * 8 >= of.numel(), n, ": uint8 [numel/8] on the device");
+  TORCH_CHECK(is_u8(*m) && m->numel() * 8 >= of.numel(), n, ": uint8 [numel/8] on the device");
+  return m->data_ptr<uint8_t>();
+}
+// The 1-bit (out > 0) mask bn_apply writes and bn_backward's mode 4 reads: exactly numel/8 bytes
+uint8_t* relu_mask(const c10::optional<at::Tensor>& m, const at::Tensor& y, const char* msg) {
+  TORCH_CHECK(m.has_value() && is_u8(*m) && m->numel() == y.numel() / 8, msg);
   return m->data_ptr<uint8_t>();
 }
 
@@ -508,6 +516,14 @@ void pack_weights_tiled(at::Tensor desc, at::Tensor tprefix, int64_t ntiles) {
 }
 
 // ------------------------------------------------------------------ BN
+// BatchNorm num_batches_tracked (optional), incremented in the finalize kernels
+static long long* num_batches_ptr(const c10::optional<at::Tensor>& nb, const at::Tensor& on) {
+  if (!nb.has_value()) return nullptr;
+  TORCH_CHECK(nb->scalar_type() == at::kLong && nb->numel() == 1 && nb->device() == on.device(),
+              "num_batches: int64 scalar on the device");
+  return (long long*)nb->data_ptr();
+}
+
 void bn_stats_finalize(at::Tensor stats, int64_t T, double count, at::Tensor gamma, at::Tensor beta,
                        c10::optional<at::Tensor> rmean, c10::optional<at::Tensor> rvar,
                        double momentum, double eps, at::Tensor scale, at::Tensor shift,
@@ -515,12 +531,7 @@ void bn_stats_finalize(at::Tensor stats, int64_t T, double count, at::Tensor gam
                        c10::optional<at::Tensor> num_batches) {
   const int C = gamma.numel();
   need_f32(stats, "stats", T * 2 * C);
-  long long* nb = nullptr;  // BatchNorm num_batches_tracked, incremented in the finalize kernel
-  if (num_batches.has_value()) {
-    TORCH_CHECK(num_batches->scalar_type() == at::kLong && num_batches->numel() == 1 &&
-                num_batches->device() == stats.device(), "num_batches: int64 scalar on the device");
-    nb = (long long*)num_batches->data_ptr();
-  }
+  long long* nb = num_batches_ptr(num_batches, stats);
   need_f32(work, "work", 256 * 2 * C);
   for (auto* t : {&gamma, &beta, &scale, &shift, &mean, &invstd}) need_f32(*t, "bn vec", C);
   const DeviceGuard guard(stats.device());
@@ -561,12 +572,7 @@ void bn_sync_finalize(at::Tensor rows, at::Tensor gamma, at::Tensor beta,
               "rows: [ws][2C+1]");
   const double* rp = need_f64(rows, "rows", rows.size(0) * (2 * C + 1));
   double* tp = need_f64(total, "total", 1);
-  long long* nb = nullptr;
-  if (num_batches.has_value()) {
-    TORCH_CHECK(num_batches->scalar_type() == at::kLong && num_batches->numel() == 1 &&
-                num_batches->device() == rows.device(), "num_batches: int64 scalar on the device");
-    nb = (long long*)num_batches->data_ptr();
-  }
+  long long* nb = num_batches_ptr(num_batches, rows);
   for (auto* t : {&gamma, &beta, &scale, &shift, &mean, &invstd}) need_f32(*t, "bn vec", C);
   if (rmean.has_value()) need_f32(*rmean, "rmean", C);
   if (rvar.has_value()) need_f32(*rvar, "rvar", C);
@@ -607,18 +613,14 @@ void bn_apply(at::Tensor y, c10::optional<at::Tensor> res, at::Tensor scale, at:
   uint8_t* mp = nullptr;
   if (mask.has_value()) {
     TORCH_CHECK(relu, "mask: ReLU outputs only");
-    TORCH_CHECK(mask->is_cuda() && mask->scalar_type() == at::kByte && mask->is_contiguous() &&
-                mask->numel() == y.numel() / 8, "mask: contiguous uint8, one byte per 8 channels");
-    mp = (uint8_t*)mask->data_ptr();
+    mp = relu_mask(mask, y, "mask: contiguous uint8, one byte per 8 channels");
   }
   dm::bn_apply(bp(y), rp, fp(scale), fp(shift), bp(out), y.numel(), C, relu, cur_stream(), mp);
 }
 
-int64_t bn_bwd_work(int64_t M, int64_t C) { return (int64_t)dm::bn_bwd_groups(M, C) * 2 * C + 3 * C + 256 * 2 * C; }
+// floats of a BatchNorm backward's work tensor: enough for any dz source of an [M][C] operand
+int64_t bn_bwd_work(int64_t M, int64_t C) { return dm::bn_bwd_work_floats(dm::bn_bwd_groups(M, C), C); }
 
-// mode: 0 no ReLU, 1 mask from `out`, 2 mask from y*scale+shift, 3 (stem) dz gathered
-// from the following max-pool's gradient (pdy, pidx; pool K/S/P) with mask from y, 4 mask
-// from the 1-bit (out > 0) mask that bn_apply wrote in the forward.
 // Stem backward without the full-resolution dy: BN-backward coefficients from the pooled-
 // domain sums (pre_slab, bn_bwd_reduce_masked), then the fused gather + apply + s2d weight
 // gradient (conv_stem.hip) into slab, then the fixed-order reduce into dw [Cout][Cin][7][7].
@@ -644,8 +646,7 @@ void stem_bwd_fused(at::Tensor y, at::Tensor mean, at::Tensor invstd, at::Tensor
   const int N = y.size(0), H = y.size(1), W = y.size(2), C = y.size(3);
   TORCH_CHECK(pdy.size(0) == N && pdy.size(1) == H / 2 && pdy.size(2) == W / 2 && pdy.size(3) == C,
               "pdy must be the 3x3/s2/p1 pooled gradient");
-  TORCH_CHECK(pidx.is_cuda() && pidx.scalar_type() == at::kByte && pidx.is_contiguous() &&
-              pidx.numel() == pdy.numel());
+  TORCH_CHECK(is_u8(pidx) && pidx.numel() == pdy.numel());
   const long long M = (long long)N * H * W;
   need_f32(work, "work", bn_bwd_work(M, C));
   need_f32(pre_slab, "pre_slab", pre_rows * 2 * C);
@@ -656,17 +657,18 @@ void stem_bwd_fused(at::Tensor y, at::Tensor mean, at::Tensor invstd, at::Tensor
   need_f32(slab, "slab", (int64_t)S * 64 * 256);
   const DeviceGuard guard(y.device());
   auto st = cur_stream();
-  // mode 3, dy = nullptr: finalize only; with pre_part the coefficients land at work[0, 3C)
-  dm::bn_backward(nullptr, nullptr, bp(y), fp(mean), fp(invstd), fp(gamma), fp(dgamma), fp(dbeta),
-                  (float)gbeta, M, C, 3, fp(scale), fp(shift), bp(pdy),
-                  (const uint8_t*)pidx.data_ptr(), H, W, H / 2, W / 2, 3, 2, 1, nullptr, nullptr,
-                  fp(work), st, fp(pre_slab), (int)pre_rows, nullptr);
-  dm::stem_wgrad_fused(bp(xs), bp(y), bp(pdy), (const uint8_t*)pidx.data_ptr(), fp(work),
+  const dm::BnBwdWork w = dm::bn_bwd_carve(fp(work), 0, C);  // pre_slab: no partial rows here
+  dm::bn_bwd_finalize(fp(pre_slab), (int)pre_rows, M, C, fp(gamma), fp(mean), fp(invstd),
+                      fp(dgamma), fp(dbeta), (float)gbeta, w.coef, w.part2, st);
+  dm::stem_wgrad_fused(bp(xs), bp(y), bp(pdy), (const uint8_t*)pidx.data_ptr(), w.coef,
                        fp(scale), fp(shift), fp(slab), N, H, W, S, st);
   dm::wgrad_reduce_s2d(fp(slab), S, C, (int)Cin, xs.size(3), fp(dw), (float)wbeta, st);
 }
 
 
+// mode (dm::BnDz): 0 no ReLU, 1 mask from `out`, 2 mask from y*scale+shift, 3 (stem) dz gathered
+// from the following max-pool's gradient (pdy, pidx; pool K/S/P) with mask from y, 4 mask
+// from the 1-bit (out > 0) mask that bn_apply wrote in the forward.
 void bn_backward(c10::optional<at::Tensor> dout, c10::optional<at::Tensor> out, at::Tensor y,
                  at::Tensor mean, at::Tensor invstd, at::Tensor gamma, at::Tensor dgamma,
                  at::Tensor dbeta, double gbeta, int64_t mode, c10::optional<at::Tensor> scale,
@@ -676,84 +678,83 @@ void bn_backward(c10::optional<at::Tensor> dout, c10::optional<at::Tensor> out, 
                  c10::optional<at::Tensor> pre_slab, int64_t pre_rows,
                  c10::optional<at::Tensor> mask, int64_t stage,
                  c10::optional<at::Tensor> sums, c10::optional<at::Tensor> total) {
-  // stage 1 / 2: the two halves of a cross-rank BatchNorm backward (see dm::bn_backward);
+  // stage 1 / 2: the two halves of a cross-rank BatchNorm backward (dm::BnStage);
   // sums [2C] float64 is written by stage 1 and read, summed over the ranks, by stage 2
   TORCH_CHECK(stage >= 0 && stage <= 2, "stage: 0 whole, 1 sums, 2 apply");
-  double* sums_p = nullptr;
-  const double* total_p = nullptr;
-  if (stage != 0) {
-    TORCH_CHECK(sums.has_value(), "stage 1 / 2 need sums");
-    sums_p = need_f64(*sums, "sums", 2 * y.size(3));
-  }
-  if (stage == 2) {
-    TORCH_CHECK(total.has_value(), "stage 2 needs total");
-    total_p = need_f64(*total, "total", 1);
-  }
+  const auto stg = (dm::BnStage)stage;
+  TORCH_CHECK(stg == dm::BnStage::Whole || sums.has_value(), "stage 1 / 2 need sums");
+  double* sums_p = stg != dm::BnStage::Whole ? need_f64(*sums, "sums", 2 * y.size(3)) : nullptr;
+  TORCH_CHECK(stg != dm::BnStage::Apply || total.has_value(), "stage 2 needs total");
+  const double* total_p = stg == dm::BnStage::Apply ? need_f64(*total, "total", 1) : nullptr;
   need_bf16_nhwc(y, "y");
   need_bf16_nhwc(dy, "dy");
   TORCH_CHECK(dy.sizes() == y.sizes());
   TORCH_CHECK(mode >= 0 && mode <= 4);
+  const auto src = (dm::BnDz)mode;
   const int C = y.size(3);
   TORCH_CHECK(C % 8 == 0 && 256 % (C / 8) == 0, "bn_backward: C/8 must divide 256");
-  const long long M = y.numel() / C;
-  need_f32(work, "work", bn_bwd_work(M, C));
+  dm::BnBwdArgs a{};
+  a.M = y.numel() / C;
+  need_f32(work, "work", bn_bwd_work(a.M, C));
   if (pre_slab.has_value()) {
     TORCH_CHECK(pre_rows >= 1, "pre_slab: >= 1 row");
     need_f32(*pre_slab, "pre_slab", pre_rows * 2 * C);
   }
-  const bf* doutp = nullptr;
-  if (mode != 3) {
+  if (src != dm::BnDz::Pool) {
     TORCH_CHECK(dout.has_value());
     need_bf16_nhwc(*dout, "dout");
     TORCH_CHECK(dout->sizes() == y.sizes());
-    doutp = bp(*dout);
+    a.dout = bp(*dout);
   }
-  const bf* outp = nullptr;
-  if (mode == 1) {
+  if (src == dm::BnDz::OutMask) {
     TORCH_CHECK(out.has_value());
     need_bf16_nhwc(*out, "out");
     TORCH_CHECK(out->sizes() == y.sizes());
-    outp = bp(*out);
+    a.out = bp(*out);
   }
-  const float *scp = nullptr, *shp = nullptr;
-  if (mode == 2 || mode == 3) {
+  if (src == dm::BnDz::YMask || src == dm::BnDz::Pool) {
     TORCH_CHECK(scale.has_value() && shift.has_value());
     need_f32(*scale, "scale", C);
     need_f32(*shift, "shift", C);
-    scp = fp(*scale);
-    shp = fp(*shift);
+    a.scale = fp(*scale); a.shift = fp(*shift);
   }
-  const bf* pdyp = nullptr;
-  const uint8_t* pidxp = nullptr;
-  int OH = 0, OW = 0;
-  if (mode == 3) {
+  if (src == dm::BnDz::Pool) {
     TORCH_CHECK(pdy.has_value() && pidx.has_value());
     need_bf16_nhwc(*pdy, "pdy");
     TORCH_CHECK(pidx->scalar_type() == at::kByte && pidx->numel() == pdy->numel());
     TORCH_CHECK(pdy->size(0) == y.size(0) && pdy->size(3) == C);
-    OH = pdy->size(1);
-    OW = pdy->size(2);
-    TORCH_CHECK(OH == (y.size(1) + 2 * P - K) / S + 1 && OW == (y.size(2) + 2 * P - K) / S + 1);
-    pdyp = bp(*pdy);
-    pidxp = (const uint8_t*)pidx->data_ptr();
+    a.OH = pdy->size(1); a.OW = pdy->size(2);
+    TORCH_CHECK(a.OH == (y.size(1) + 2 * P - K) / S + 1 && a.OW == (y.size(2) + 2 * P - K) / S + 1);
+    a.pdy = bp(*pdy); a.pidx = (const uint8_t*)pidx->data_ptr();
   }
-  const uint8_t* mp = nullptr;
-  if (mode == 4) {
-    TORCH_CHECK(mask.has_value() && mask->is_cuda() && mask->scalar_type() == at::kByte &&
-                mask->is_contiguous() && mask->numel() == y.numel() / 8, "mode 4 needs the uint8 mask");
-    mp = (const uint8_t*)mask->data_ptr();
-  }
+  if (src == dm::BnDz::BitMask) a.mask = relu_mask(mask, y, "mode 4 needs the uint8 mask");
   bf* drp = nullptr;
   if (dres.has_value()) {
     need_bf16_nhwc(*dres, "dres");
     TORCH_CHECK(dres->sizes() == y.sizes(), "dres: the shape of y");
     drp = bp(*dres);
   }
+  a.y = bp(y); a.mean = fp(mean); a.invstd = fp(invstd);
+  a.H = y.size(1); a.W = y.size(2); a.K = K; a.S = S; a.P = P; a.C = C;
   const DeviceGuard guard(y.device());
-  dm::bn_backward(doutp, outp, bp(y), fp(mean), fp(invstd), fp(gamma), fp(dgamma), fp(dbeta),
-                  (float)gbeta, M, C, (int)mode, scp, shp, pdyp, pidxp, y.size(1), y.size(2), OH,
-                  OW, K, S, P, bp(dy), drp, fp(work), cur_stream(), pre_slab.has_value() ? fp(*pre_slab) : nullptr,
-                  (int)pre_rows, mp, (int)stage, sums_p, total_p);
+  auto st = cur_stream();
+  float *gm = fp(gamma), *dg = fp(dgamma), *db = fp(dbeta);
+  // the partial rows are the reduce's own unless a producing kernel left them (pre_slab) or,
+  // in stage 2, the sums of all ranks replace them
+  const bool reduce = !pre_slab.has_value() && stg != dm::BnStage::Apply;
+  const dm::BnBwdWork w =
+      dm::bn_bwd_carve(fp(work), reduce ? dm::bn_bwd_rows(src, a, drp != nullptr) : 0, C);
+  if (stg == dm::BnStage::Apply) {
+    dm::bn_bwd_coef(sums_p, total_p, gm, a.mean, a.invstd, C, w.coef, st);
+  } else {
+    const float* part = reduce ? w.part : fp(*pre_slab);
+    const int rows = reduce ? dm::bn_bwd_reduce(src, a, drp != nullptr, w.part, st) : (int)pre_rows;
+    if (stg == dm::BnStage::Sums)
+      return dm::bn_bwd_sums(part, rows, C, dg, db, (float)gbeta, sums_p, w.part2, st);
+    dm::bn_bwd_finalize(part, rows, a.M, C, gm, a.mean, a.invstd, dg, db, (float)gbeta, w.coef,
+                        w.part2, st);
+  }
+  dm::bn_bwd_apply(src, a, w.coef, bp(dy), drp, st);
 }
 
 // Stage "sums" of a coefficient-only BatchNorm backward (the fused stem): dgamma / dbeta from
@@ -764,13 +765,11 @@ void bn_bwd_sums(at::Tensor pre_slab, int64_t pre_rows, int64_t C, at::Tensor dg
   need_f32(pre_slab, "pre_slab", pre_rows * 2 * C);
   need_f32(dgamma, "dgamma", C);
   need_f32(dbeta, "dbeta", C);
-  need_f32(work, "work", 3 * C + 256 * 2 * C);
+  need_f32(work, "work", dm::bn_bwd_work_floats(0, C));
   double* sp = need_f64(sums, "sums", 2 * C);
   const DeviceGuard guard(pre_slab.device());
-  dm::bn_backward(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, fp(dgamma), fp(dbeta),
-                  (float)gbeta, 0, (int)C, 3, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 3, 2,
-                  1, nullptr, nullptr, fp(work), cur_stream(), fp(pre_slab), (int)pre_rows, nullptr,
-                  1, sp, nullptr);
+  dm::bn_bwd_sums(fp(pre_slab), (int)pre_rows, (int)C, fp(dgamma), fp(dbeta), (float)gbeta, sp,
+                  dm::bn_bwd_carve(fp(work), 0, C).part2, cur_stream());
 }
 
 void bn_relu_maxpool(at::Tensor y, at::Tensor scale, at::Tensor shift, at::Tensor out,
@@ -809,11 +808,12 @@ int64_t bn_bwd_reduce_masked(at::Tensor dout, at::Tensor y, at::Tensor mean, at:
   need_f32(invstd, "invstd", C);
   need_f32(scale, "scale", C);
   need_f32(shift, "shift", C);
-  const long long M = y.numel() / C;
-  need_f32(part, "part", (int64_t)dm::bn_bwd_groups(M, C) * 2 * C);
+  dm::BnBwdArgs a{};
+  a.dout = bp(dout); a.y = bp(y); a.mean = fp(mean); a.invstd = fp(invstd);
+  a.scale = fp(scale); a.shift = fp(shift); a.M = y.numel() / C; a.C = C;
+  need_f32(part, "part", (int64_t)dm::bn_bwd_rows(dm::BnDz::YMask, a, false) * 2 * C);
   const DeviceGuard guard(y.device());
-  return dm::bn_bwd_reduce_masked(bp(dout), bp(y), fp(mean), fp(invstd), fp(scale), fp(shift), M,
-                                  C, fp(part), cur_stream());
+  return dm::bn_bwd_reduce(dm::BnDz::YMask, a, false, fp(part), cur_stream());
 }
 
 // ------------------------------------------------------------------ pooling / packing
@@ -985,8 +985,8 @@ void stem_bwd_fused2(at::Tensor img, c10::optional<at::Tensor> idx, std::vector<
                      at::Tensor dbeta, double gbeta, at::Tensor pre_slab, int64_t pre_rows,
                      at::Tensor dw, double wbeta, at::Tensor work, at::Tensor dslab, int64_t grid,
                      c10::optional<at::Tensor> bn_sums, c10::optional<at::Tensor> bn_total) {
-  // bn_sums + bn_total (cross-rank BatchNorm): the coefficients come from the global sums (stage
-  // "apply" of dm::bn_backward); dgamma / dbeta were written by bn_bwd_sums and stay untouched
+  // bn_sums + bn_total (cross-rank BatchNorm): the coefficients come from the global sums
+  // (dm::bn_bwd_coef); dgamma / dbeta were written by bn_bwd_sums and stay untouched
   TORCH_CHECK(bn_sums.has_value() == bn_total.has_value(), "sums and total: both or neither");
   const ImgView v = img_view(img);
   TORCH_CHECK(dm::stem_fused_supported(v.H, v.W), "fused stem: unsupported input size");
@@ -1007,20 +1007,21 @@ void stem_bwd_fused2(at::Tensor img, c10::optional<at::Tensor> idx, std::vector<
   const float b3[3] = {(float)nbi[0], (float)nbi[1], (float)nbi[2]};
   const DeviceGuard guard(pdy.device());
   auto st = cur_stream();
-  // mode 3, dy = nullptr: coefficients only (work[0, 3C) = a, b, cc) + dgamma / dbeta
-  dm::bn_backward(nullptr, nullptr, nullptr, fp(mean), fp(invstd), fp(gamma), fp(dgamma), fp(dbeta),
-                  (float)gbeta, M, C, 3, nullptr, nullptr, nullptr, nullptr, v.H / 2, v.W / 2,
-                  v.H / 4, v.W / 4, 3, 2, 1, nullptr, nullptr, fp(work), st, fp(pre_slab),
-                  (int)pre_rows, nullptr, bn_sums.has_value() ? 2 : 0,
-                  bn_sums.has_value() ? need_f64(*bn_sums, "sums", 2 * C) : nullptr,
-                  bn_total.has_value() ? need_f64(*bn_total, "total", 1) : nullptr);
+  // the coefficients (a, b, cc) only: the kernels below apply them
+  const dm::BnBwdWork w = dm::bn_bwd_carve(fp(work), 0, C);  // pre_slab: no partial rows here
+  if (bn_sums.has_value())
+    dm::bn_bwd_coef(need_f64(*bn_sums, "sums", 2 * C), need_f64(*bn_total, "total", 1), fp(gamma),
+                    fp(mean), fp(invstd), C, w.coef, st);
+  else
+    dm::bn_bwd_finalize(fp(pre_slab), (int)pre_rows, M, C, fp(gamma), fp(mean), fp(invstd),
+                        fp(dgamma), fp(dbeta), (float)gbeta, w.coef, w.part2, st);
   float* d_part = fp(dslab);
   float* g_part = d_part + grid * C * dm::stem_slab_cols();
   float* sums = g_part + grid * dm::stem_gram_cols() * dm::stem_gram_cols();
   dm::stem_bwd_fused2(v.ptr, v.dtype, idx_ptr(idx, B, v.N), s3, b3, bp(wk), bp(pdy),
                       (const uint8_t*)code4.data_ptr(), d_part, g_part, B, v.N, v.H, v.W,
                       (int)grid, st);
-  dm::stem_wcombine(d_part, g_part, (int)grid, bp(wk), fp(work), sums, fp(dw), (float)wbeta, st);
+  dm::stem_wcombine(d_part, g_part, (int)grid, bp(wk), w.coef, sums, fp(dw), (float)wbeta, st);
 }
 
 void stem_pack_weights(at::Tensor w, at::Tensor wk) {

@@ -9,6 +9,7 @@
 // upstream grad) and an apply pass dy = a·dz + b·y + c that also emits the residual
 // branch gradient dz when the block has a skip connection.
 #include "common.h"
+#include "kernels.h"
 
 namespace dm {
 
@@ -378,28 +379,8 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const bf16_t* __restrict_
 }
 
 // ------------------------------------------------------------------ BN backward
-// dz = upstream grad with the ReLU mask; sources (template MODE):
-//   0  dout tensor, no ReLU
-//   1  dout tensor, mask from the saved output (out > 0)          -- residual layers
-//   2  dout tensor, mask recomputed from y (y*scale + shift > 0)   -- no `out` read
-//   3  gathered from a following 3x3/s2 max-pool's grads + argmax codes, mask from y
-//      (stem: neither `out` nor the unpooled gradient is ever materialised)
-//   4  dout tensor, mask from the forward's 1-bit (out > 0) mask    -- residual layers
-struct BnBwdArgs {
-  const bf16_t* dout;
-  const bf16_t* out;
-  const bf16_t* y;
-  const float* mean;
-  const float* invstd;
-  const float* scale;   // forward BN scale/shift (modes 2, 3)
-  const float* shift;
-  const bf16_t* pdy;    // mode 3: pooled-output gradient [N][OH][OW][C]
-  const uint8_t* pidx;  //         argmax codes (kh*K + kw), same shape
-  int H, W, OH, OW, K, S, P;
-  long long M;
-  int C;
-  const uint8_t* mask;  // mode 4: bit j of byte i = (out > 0) of chunk i, channel j
-};
+// dz = upstream grad with the ReLU mask; the template MODE of the kernels below is the value of
+// its source, BnDz (kernels.h, with the operand description BnBwdArgs)
 
 // mode 3: dz of one 8-channel chunk of input pixel r, gathered from the pool windows
 // that contain it.  For K <= 2S a pixel lies in at most 2 x 2 windows: all candidate
@@ -1284,7 +1265,6 @@ void bn_apply(const bf16_t* y, const bf16_t* res, const float* scale, const floa
   }
 }
 
-int bn_bwd_groups(long long M, int C);
 int bn_bwd_groups(long long M, int C) {
   const int RL = 256 / (C / 8);
   // >= 16 rows per row lane (4 batched iterations): enough workgroups to keep every CU
@@ -1295,75 +1275,85 @@ int bn_bwd_groups(long long M, int C) {
   return (int)g;
 }
 
-void bn_backward(const bf16_t* dout, const bf16_t* out, const bf16_t* y, const float* mean,
-                 const float* invstd, const float* gamma, float* dgamma, float* dbeta,
-                 float gbeta, long long M, int C, int mode, const float* scale,
-                 const float* shift, const bf16_t* pdy, const uint8_t* pidx, int H, int W,
-                 int OH, int OW, int K, int S, int P, bf16_t* dy, bf16_t* dres, float* work,
-                 hipStream_t st, const float* pre_part, int pre_rows, const uint8_t* mask,
-                 int stage, double* sums, const double* total) {
-  // stage (cross-rank BatchNorm): 0 = the whole backward; 1 = "sums": the reduction (or
-  // pre_part), dgamma / dbeta from this rank's sums, and sums [2C] float64 out -- nothing else;
-  // 2 = "apply": no reduction, dgamma / dbeta untouched, the coefficients from the global `sums`
-  // and the device scalar `total` into work[0, 3C), then the apply kernels as in stage 0
-  // pre_part (optional): [pre_rows][2C] partial Σdz, Σdz·x̂ already reduced by the producing
-  // kernel (the stem's pooled-domain sums) — the reduction pass over dout and y is skipped
-  // work: [G][2C] partials + [3C] coefficients + [<=256][2C] second-level partials
-  BnBwdArgs a{dout, out, y, mean, invstd, scale, shift, pdy, pidx, H, W, OH, OW, K, S, P, M, C,
-              mask};
-  // stem 3x3/s2/p1 pool with even H, W: quad gather (4 pixels share their 4 windows)
-  const bool quad = mode == 3 && K == 3 && S == 2 && P == 1 && H % 2 == 0 && W % 2 == 0 &&
-                    OH == H / 2 && OW == W / 2 && !dres && (long long)M * C / 8 < (1LL << 31);
-  const int G = pre_part ? pre_rows : quad ? bn_bwd_groups(M / 4, C) : bn_bwd_groups(M, C);
-  float* part = pre_part ? const_cast<float*>(pre_part) : work;
-  float* coef = (pre_part || stage == 2) ? work : work + (long long)G * 2 * C;
-  float* part2 = coef + 3 * C;
-  const size_t shr = sizeof(float) * (256 * 16 + 2 * C);
-  if (stage == 2) {
-    bn_bwd_coef_kernel<<<(C + 255) / 256, 256, 0, st>>>(sums, total, gamma, mean, invstd, C, coef);
-  } else if (pre_part) {
-  } else if (quad) bn_bwd_reduce_quad_kernel<<<G, 256, shr, st>>>(a, part);
-  else switch (mode) {
+// The BatchNorm backward as separate steps (kernels.h); the bindings chain them.  Whole:
+// reduce -> finalize -> apply.  Across ranks: reduce -> sums, then, once the sums of all ranks
+// are added, coef -> apply.  A producing kernel that leaves pre-reduced partial rows (a dgrad
+// epilogue's BnBwdRed, the stem's pooled-domain sums) stands in for the reduce; the fused stem
+// kernels stand in for the apply.
+// stem 3x3/s2/p1 pool with even H, W: quad gather (4 pixels share their 4 windows)
+static bool bn_bwd_quad(BnDz src, const BnBwdArgs& a, bool dres) {
+  return src == BnDz::Pool && a.K == 3 && a.S == 2 && a.P == 1 && a.H % 2 == 0 && a.W % 2 == 0 &&
+         a.OH == a.H / 2 && a.OW == a.W / 2 && !dres && a.M * a.C / 8 < (1LL << 31);
+}
+
+int bn_bwd_rows(BnDz src, const BnBwdArgs& a, bool dres) {
+  return bn_bwd_groups(bn_bwd_quad(src, a, dres) ? a.M / 4 : a.M, a.C);
+}
+
+int bn_bwd_reduce(BnDz src, const BnBwdArgs& a, bool dres, float* part, hipStream_t st) {
+  const int G = bn_bwd_rows(src, a, dres);
+  const size_t shr = sizeof(float) * (256 * 16 + 2 * a.C);
+  if (bn_bwd_quad(src, a, dres)) bn_bwd_reduce_quad_kernel<<<G, 256, shr, st>>>(a, part);
+  else switch (src) {
     // 4 16-B chunks per operand in flight per thread (8 measured neutral for the reduce and
     // forward apply, -1.2 % for the backward apply: profiles/bn_loads_in_flight_r2c.jsonl)
     // non-temporal loads: the reduce streams its inputs once (the apply pass re-reads them
     // from HBM either way at these sizes)
-    case 0: bn_bwd_reduce_kernel<0, 4, true><<<G, 256, shr, st>>>(a, part); break;
-    case 1: bn_bwd_reduce_kernel<1, 4, true><<<G, 256, shr, st>>>(a, part); break;
-    case 2: bn_bwd_reduce_kernel<2, 4, true><<<G, 256, shr, st>>>(a, part); break;
-    case 4: bn_bwd_reduce_kernel<4, 4, true><<<G, 256, shr, st>>>(a, part); break;
-    default: bn_bwd_reduce_kernel<3><<<G, 256, shr, st>>>(a, part); break;
+    case BnDz::Plain: bn_bwd_reduce_kernel<0, 4, true><<<G, 256, shr, st>>>(a, part); break;
+    case BnDz::OutMask: bn_bwd_reduce_kernel<1, 4, true><<<G, 256, shr, st>>>(a, part); break;
+    case BnDz::YMask: bn_bwd_reduce_kernel<2, 4, true><<<G, 256, shr, st>>>(a, part); break;
+    case BnDz::BitMask: bn_bwd_reduce_kernel<4, 4, true><<<G, 256, shr, st>>>(a, part); break;
+    case BnDz::Pool: bn_bwd_reduce_kernel<3><<<G, 256, shr, st>>>(a, part); break;
   }
-  if (stage != 2) {
-    const int G2 = colsum_groups(G);
-    const FinBwd fb{gamma, mean, invstd, dgamma, dbeta, gbeta, coef};
-    const float* fin = part;
-    if (G2) {  // parallel fixed-order pre-reduction so the finalize sums stay short
-      slab_colsum_kernel<<<dim3((2 * C + 63) / 64, G2), 256, 0, st>>>(part, G, 2 * C, part2);
-      fin = part2;
-    }
-    const int rows = G2 ? G2 : G;
-    if (stage == 1) {
-      if (rows > 256)
-        bn_bwd_sums_kernel<256, 4><<<(C + 3) / 4, 256, 0, st>>>(fin, rows, C, dgamma, dbeta, gbeta,
-                                                                sums);
-      else
-        bn_bwd_sums_kernel<256, FIN_CH><<<(C + FIN_CH - 1) / FIN_CH, 256, 0, st>>>(
-            fin, rows, C, dgamma, dbeta, gbeta, sums);
-      return;
-    }
-    if (rows > 256)
-      bn_bwd_finalize_kernel<256, 4><<<(C + 3) / 4, 256, 0, st>>>(fin, rows, C, (double)M, fb);
-    else
-      bn_bwd_finalize_kernel<256, FIN_CH><<<(C + FIN_CH - 1) / FIN_CH, 256, 0, st>>>(fin, rows, C,
-                                                                              (double)M, fb);
-  }
-  if (!dy) return;  // coefficients only: stem_bwd_fused / stem_bwd_fused2 apply dy themselves
-  const long long n8 = M * C / 8;
+  return G;
+}
+
+// parallel fixed-order pre-reduction so the finalize sums stay short: past FIN_DIRECT_ROWS rows,
+// part2 and its row count replace part's
+static const float* bn_bwd_prereduce(const float* part, int& rows, int C, float* part2,
+                                     hipStream_t st) {
+  const int G2 = colsum_groups(rows);
+  if (!G2) return part;
+  slab_colsum_kernel<<<dim3((2 * C + 63) / 64, G2), 256, 0, st>>>(part, rows, 2 * C, part2);
+  rows = G2;
+  return part2;
+}
+
+void bn_bwd_sums(const float* part, int rows, int C, float* dgamma, float* dbeta, float gbeta,
+                 double* sums, float* part2, hipStream_t st) {
+  const float* fin = bn_bwd_prereduce(part, rows, C, part2, st);
+  if (rows > 256)
+    bn_bwd_sums_kernel<256, 4><<<(C + 3) / 4, 256, 0, st>>>(fin, rows, C, dgamma, dbeta, gbeta,
+                                                            sums);
+  else
+    bn_bwd_sums_kernel<256, FIN_CH><<<(C + FIN_CH - 1) / FIN_CH, 256, 0, st>>>(
+        fin, rows, C, dgamma, dbeta, gbeta, sums);
+}
+
+void bn_bwd_finalize(const float* part, int rows, long long M, int C, const float* gamma,
+                     const float* mean, const float* invstd, float* dgamma, float* dbeta,
+                     float gbeta, float* coef, float* part2, hipStream_t st) {
+  const FinBwd fb{gamma, mean, invstd, dgamma, dbeta, gbeta, coef};
+  const float* fin = bn_bwd_prereduce(part, rows, C, part2, st);
+  if (rows > 256)
+    bn_bwd_finalize_kernel<256, 4><<<(C + 3) / 4, 256, 0, st>>>(fin, rows, C, (double)M, fb);
+  else
+    bn_bwd_finalize_kernel<256, FIN_CH><<<(C + FIN_CH - 1) / FIN_CH, 256, 0, st>>>(fin, rows, C,
+                                                                            (double)M, fb);
+}
+
+void bn_bwd_coef(const double* sums, const double* total, const float* gamma, const float* mean,
+                 const float* invstd, int C, float* coef, hipStream_t st) {
+  bn_bwd_coef_kernel<<<(C + 255) / 256, 256, 0, st>>>(sums, total, gamma, mean, invstd, C, coef);
+}
+
+void bn_bwd_apply(BnDz src, const BnBwdArgs& a, const float* coef, bf16_t* dy, bf16_t* dres,
+                  hipStream_t st) {
+  const long long n8 = a.M * a.C / 8;
   // grid-strided mode 3: workgroup cap 4096 (1024-8192 within noise,
   // profiles/bn_bwd_apply_grid_ab_r3s3.txt)
   const int grid = grid_for(n8, 256, 4096);
-  const size_t sh = sizeof(float) * 5 * C;
+  const size_t sh = sizeof(float) * 5 * a.C;
   // streaming modes: flat blocks of 4 x 256 chunks, non-temporal (see bn_apply_kernel); the
   // stem's pool-gather mode keeps its grid-strided loop
   const int gflat = (int)((n8 + 4 * 256 - 1) / (4 * 256));
@@ -1374,11 +1364,11 @@ void bn_backward(const bf16_t* dout, const bf16_t* out, const bf16_t* y, const f
     else                                                                                           \
       bn_bwd_apply_kernel<MD, D><<<grid, 256, sh, st>>>(a, coef, dy, dres);                        \
   } while (0)
-  if (quad) {
+  if (bn_bwd_quad(src, a, dres)) {
     bn_bwd_apply_quad_kernel<<<grid_for(n8 / 4, 256, 4096), 256, sh, st>>>(a, coef, dy);
     return;
   }
-  switch (mode * 2 + (dres ? 1 : 0)) {
+  switch ((int)src * 2 + (dres ? 1 : 0)) {
     case 0: DM_BNB(0, false); break;
     case 1: DM_BNB(0, true); break;
     case 2: DM_BNB(1, false); break;
@@ -1392,7 +1382,6 @@ void bn_backward(const bf16_t* dout, const bf16_t* out, const bf16_t* y, const f
   }
 #undef DM_BNB
 }
-
 
 void bn_relu_maxpool(const bf16_t* y, const float* scale, const float* shift, bf16_t* out,
                      uint8_t* idx, int N, int H, int W, int C, int OH, int OW, int K, int S,
@@ -1410,20 +1399,6 @@ void bn_relu_maxpool(const bf16_t* y, const float* scale, const float* shift, bf
   }
   bn_relu_maxpool_kernel<<<grid_for(total, 256, 8192), 256, sizeof(float) * 2 * C, st>>>(
       y, scale, shift, out, idx, yarg, N, H, W, C, OH, OW, K, S, P);
-}
-
-// Σdz, Σdz·x̂ partial rows [G][2C] of a mode-2 operand pair (dz = dout masked by
-// y*scale + shift > 0) over M rows; returns G (= bn_bwd_groups(M, C)).  Used for the stem's
-// pooled-domain sums (dout = pooled grad, y = yarg), handed to bn_backward as pre_part.
-int bn_bwd_reduce_masked(const bf16_t* dout, const bf16_t* y, const float* mean,
-                         const float* invstd, const float* scale, const float* shift, long long M,
-                         int C, float* part, hipStream_t st) {
-  BnBwdArgs a{dout, nullptr, y, mean, invstd, scale, shift, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0,
-              M, C, nullptr};
-  const int G = bn_bwd_groups(M, C);
-  const size_t shr = sizeof(float) * (256 * 16 + 2 * C);
-  bn_bwd_reduce_kernel<2, 4, true><<<G, 256, shr, st>>>(a, part);
-  return G;
 }
 
 void maxpool_fwd(const bf16_t* x, bf16_t* y, uint8_t* idx, int N, int H, int W, int C, int OH,

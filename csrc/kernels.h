@@ -180,7 +180,7 @@ void stem_pack_weights(const float* w, bf16_t* wk, hipStream_t st);
 // The BatchNorm backward reduction of the layer whose output gradient a data gradient
 // produces, done in that dgrad's epilogue: with dz = Y * relu-mask (mask from y*sc + sh > 0,
 // or the 1-bit `mask` when set), part[wg][0][c] = Σ dz and part[wg][1][c] = Σ dz (y - mu) is
-// (one row per workgroup, the layout bn_backward's pre_part consumes)
+// (one row per workgroup, the pre-reduced rows bn_bwd_finalize / bn_bwd_sums consume)
 struct BnBwdRed {
   const bf16_t* y;
   const uint8_t* mask;
@@ -257,15 +257,61 @@ void bn_eval_coeffs(const float* gamma, const float* beta, const float* rmean, c
                     float eps, int C, float* scale, float* shift, hipStream_t st);
 void bn_apply(const bf16_t* y, const bf16_t* res, const float* scale, const float* shift,
               bf16_t* out, long long n, int C, bool relu, hipStream_t st, uint8_t* mask = nullptr);
+// BatchNorm backward, as the steps the bindings chain: reduce -> finalize -> apply; across
+// ranks reduce -> sums, the all-reduce of sums [2C] float64, then coefficients -> apply.
+// dz = the upstream gradient under the ReLU mask; its source is the kernels' MODE:
+//   0 Plain    dout tensor, no ReLU
+//   1 OutMask  dout tensor, mask from the saved output (out > 0)          -- residual layers
+//   2 YMask    dout tensor, mask recomputed from y (y*scale + shift > 0)   -- no `out` read
+//   3 Pool     gathered from a following max-pool's grads + argmax codes, mask from y
+//              (stem: neither `out` nor the unpooled gradient is ever materialised)
+//   4 BitMask  dout tensor, mask from the forward's 1-bit (out > 0) mask    -- residual layers
+enum class BnDz { Plain, OutMask, YMask, Pool, BitMask };
+// which half of a cross-rank backward a caller asks for (Sums writes sums, Apply reads them)
+enum class BnStage { Whole, Sums, Apply };
+struct BnBwdArgs {
+  const bf16_t* dout;
+  const bf16_t* out;
+  const bf16_t* y;
+  const float* mean;
+  const float* invstd;
+  const float* scale;   // forward BN scale/shift (modes 2, 3)
+  const float* shift;
+  const bf16_t* pdy;    // mode 3: pooled-output gradient [N][OH][OW][C]
+  const uint8_t* pidx;  //         argmax codes (kh*K + kw), same shape
+  int H, W, OH, OW, K, S, P;
+  long long M;
+  int C;
+  const uint8_t* mask;  // mode 4: bit j of byte i = (out > 0) of chunk i, channel j
+};
+// The workspace of one backward: part [rows][2C] (the reduce's partial rows; rows = 0 when they
+// come pre-reduced from a producing kernel, or the sums from the other ranks), coef [3C]
+// (dy = a dz + b y + cc), part2 [<= 256][2C] (the finalize's second-level partials)
+struct BnBwdWork { float *part, *coef, *part2; };
+inline long long bn_bwd_work_floats(int rows, int C) { return (2LL * rows + 3 + 2 * 256) * C; }
+inline BnBwdWork bn_bwd_carve(float* work, int rows, int C) {
+  float* coef = work + 2LL * rows * C;
+  return {work, coef, coef + 3 * C};
+}
 int bn_bwd_groups(long long M, int C);
-void bn_backward(const bf16_t* dout, const bf16_t* out, const bf16_t* y, const float* mean,
-                 const float* invstd, const float* gamma, float* dgamma, float* dbeta,
-                 float gbeta, long long M, int C, int mode, const float* scale,
-                 const float* shift, const bf16_t* pdy, const uint8_t* pidx, int H, int W,
-                 int OH, int OW, int K, int S, int P, bf16_t* dy, bf16_t* dres, float* work,
-                 hipStream_t st, const float* pre_part = nullptr, int pre_rows = 0,
-                 const uint8_t* mask = nullptr, int stage = 0, double* sums = nullptr,
-                 const double* total = nullptr);
+// rows the reduce writes.  dres (the apply also emits the residual branch's dz) only enters
+// through the choice of the stem's quad kernels, which the reduce and the apply must make alike
+int bn_bwd_rows(BnDz src, const BnBwdArgs& a, bool dres);
+// part [rows][2C] = partial Σdz, Σdz·x̂ over a's M rows; returns rows
+int bn_bwd_reduce(BnDz src, const BnBwdArgs& a, bool dres, float* part, hipStream_t st);
+// dgamma / dbeta (gbeta: accumulate) and coef from the partial rows of M elements per channel
+void bn_bwd_finalize(const float* part, int rows, long long M, int C, const float* gamma,
+                     const float* mean, const float* invstd, float* dgamma, float* dbeta,
+                     float gbeta, float* coef, float* part2, hipStream_t st);
+// cross-rank: dgamma / dbeta from this rank's rows and sums [2C] float64 out; then coef from the
+// sums of all ranks and the device scalar total (Σ of the ranks' M)
+void bn_bwd_sums(const float* part, int rows, int C, float* dgamma, float* dbeta, float gbeta,
+                 double* sums, float* part2, hipStream_t st);
+void bn_bwd_coef(const double* sums, const double* total, const float* gamma, const float* mean,
+                 const float* invstd, int C, float* coef, hipStream_t st);
+// dy = a dz + b y + cc, and dres = dz when set
+void bn_bwd_apply(BnDz src, const BnBwdArgs& a, const float* coef, bf16_t* dy, bf16_t* dres,
+                  hipStream_t st);
 // cross-rank BatchNorm forward: this rank's float64 row [mean (C) | M2 (C) | n] from its
 // statistics slab; then the merge of all ranks' rows [ws][2C+1] in rank order (total = Σn)
 void bn_sync_local(const float* stats, int T, int C, double count, double* row, float* work,
@@ -277,9 +323,6 @@ void bn_sync_finalize(const double* rows, int ws, int C, const float* gamma, con
 void bn_relu_maxpool(const bf16_t* y, const float* scale, const float* shift, bf16_t* out,
                      uint8_t* idx, int N, int H, int W, int C, int OH, int OW, int K, int S,
                      int P, hipStream_t st, bf16_t* yarg = nullptr);
-int bn_bwd_reduce_masked(const bf16_t* dout, const bf16_t* y, const float* mean,
-                         const float* invstd, const float* scale, const float* shift, long long M,
-                         int C, float* part, hipStream_t st);
 void maxpool_fwd(const bf16_t* x, bf16_t* y, uint8_t* idx, int N, int H, int W, int C, int OH,
                  int OW, int K, int S, int P, hipStream_t st);
 void maxpool_bwd(const bf16_t* dy, const uint8_t* idx, bf16_t* dx, int N, int H, int W, int C,
