@@ -1,6 +1,7 @@
 // Bindings for the NHWC bf16 ResNet kernels: implicit-GEMM conv (fwd / dgrad /
-// wgrad), BatchNorm, pooling, input/weight packing.  Geometry (ConvGeom) is built
-// here on the host from plain conv parameters, so Python never sees kernel structs.
+// wgrad), BatchNorm, pooling, input/weight packing.  The conv bindings check their operands,
+// build the geometry (conv_geom.h) from plain conv parameters, so Python never sees kernel
+// structs, and hand both to the dispatcher (conv_launch.cpp), which picks the kernel.
 #include <torch/extension.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -8,8 +9,6 @@
 #include <map>
 #include <mutex>
 
-#include "conv_cfg.h"
-#include "conv_geom.h"
 #include "kernels.h"
 
 namespace {
@@ -34,43 +33,26 @@ void need_f32(const at::Tensor& t, const char* n, int64_t numel = -1) {
               " must be a contiguous fp32 HIP tensor");
   if (numel >= 0) TORCH_CHECK(t.numel() >= numel, n, " too small");
 }
-int ilog2(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  TORCH_CHECK((1 << l) == v, "C/8 must be a power of two");
-  return l;
-}
-
-dm::ConvGeom fwd_geom(const at::Tensor& x, int Cout, int KH, int KW, int stride, int pad, int OH,
-                      int OW) {
-  dm::ConvGeom g{};
-  g.N = x.size(0); g.H = x.size(1); g.W = x.size(2); g.C = x.size(3);
-  g.lgC8 = ilog2(g.C / 8);
-  g.Hg = OH; g.Wg = OW; g.isy = stride; g.isx = stride;
-  g.OH = OH; g.OW = OW; g.OC = Cout; g.osy = 1; g.osx = 1; g.oy0 = 0; g.ox0 = 0;
-  g.nth = KH; g.ntw = KW; g.dy0 = -pad; g.dys = 1; g.dx0 = -pad; g.dxs = 1;
-  g.kh0 = 0; g.khs = 1; g.kw0 = 0; g.kws = 1; g.KW = KW;
-  g.Ncols = Cout; g.wK = KH * KW * g.C;
-  g.M = (long long)g.N * OH * OW;
-  g.K = KH * KW * g.C;
-  TORCH_CHECK(KH * KW <= dm::MAXTAPS, "too many taps");
-  dm::geom_finalize(g);
+// the forward geometry of a conv over x [N,H,W,C] (conv_geom.h), its complaints raised
+dm::ConvGeom fwd_geom(int N, int H, int W, int C, int Cout, int KH, int KW, int stride, int pad,
+                      int OH, int OW) {
+  dm::ConvGeom g;
+  const char* err = dm::conv_fwd_geom(g, N, H, W, C, Cout, KH, KW, stride, pad, OH, OW);
+  TORCH_CHECK(!err, err);
   return g;
 }
 
 // the rows of csrc/conv_cfg.h behind a cfg argument
-const dm::ConvCfg& cfg_of(int64_t cfg) {
-  const dm::ConvCfg* c = dm::conv_cfg((int)cfg);
+template <class Row>
+const Row& row_of(const Row* c, int64_t cfg) {
   TORCH_CHECK(c, "unknown cfg ", cfg);
   return *c;
 }
+const dm::ConvCfg& cfg_of(int64_t cfg) { return row_of(dm::conv_cfg((int)cfg), cfg); }
+const dm::WgradCfg& wgrad_cfg_of(int64_t cfg) { return row_of(dm::wgrad_cfg((int)cfg), cfg); }
 
-// statistics rows a forward conv of this cfg writes (one per row tile, or per workgroup of the
-// persistent res64 kernel)
-int64_t conv_stats_rows(int64_t M, int64_t cfg) {
-  const int bm = cfg_of(cfg).rowtile;
-  return bm ? (M + bm - 1) / bm : dm::res64_grid(M);
-}
+// statistics rows a forward conv of this cfg writes
+int64_t conv_stats_rows(int64_t M, int64_t cfg) { return dm::conv_stats_rows(M, cfg_of(cfg)); }
 
 bool is_u8(const at::Tensor& t) {
   return t.is_cuda() && t.scalar_type() == at::kByte && t.is_contiguous();
@@ -179,86 +161,16 @@ void conv_fwd(at::Tensor x, at::Tensor wpack, at::Tensor y, c10::optional<at::Te
               "output spatial size mismatch");
   TORCH_CHECK(wpack.scalar_type() == at::kBFloat16 && wpack.numel() == (int64_t)Cout * KH * KW * x.size(3),
               "wpack must be bf16 [Cout][KH][KW][C]");
-  auto g = fwd_geom(x, Cout, KH, KW, stride, pad, OH, OW);
-  const dm::ConvCfg* c = &cfg_of(cfg);
-  float* sp = nullptr;
+  auto g = fwd_geom(x.size(0), x.size(1), x.size(2), x.size(3), Cout, KH, KW, stride, pad, OH, OW);
+  dm::ConvOperands ops{bp(x), bp(wpack), bp(y), pipe_sched(balance)};
   if (stats.has_value()) {
     need_f32(*stats, "stats", conv_stats_rows(g.M, cfg) * 2 * Cout);
-    sp = fp(*stats);
+    ops.stats = fp(*stats);
   }
-  const bf* ap = nullptr;
-  if (add.has_value()) { need_bf16_nhwc(*add, "add"); TORCH_CHECK(add->sizes() == y.sizes()); ap = bp(*add); }
+  if (add.has_value()) { need_bf16_nhwc(*add, "add"); TORCH_CHECK(add->sizes() == y.sizes()); ops.add = bp(*add); }
+  if (pre_scale.has_value()) std::tie(ops.pre_sc, ops.pre_sh) = pre_bn(pre_scale, pre_shift, x);
   const DeviceGuard guard(x.device());
-  if (pre_scale.has_value()) {
-    const auto [psc, psh] = pre_bn(pre_scale, pre_shift, x);
-    // a tile that takes no fused pre-BN may name the one (same statistics slab rows) that does
-    if (c->pre_reroute) c = &cfg_of(c->pre_reroute);
-    if (c->pre_bn && c->family == dm::ConvFamily::res64) {
-      dm::conv_res64(bp(x), bp(wpack), bp(y), ap, sp, g, cur_stream(), psc, psh);
-      return;
-    }
-    TORCH_CHECK(c->pre_bn && c->family == dm::ConvFamily::halo && dm::conv_halo_supported(g),
-                "fused pre-BN needs a halo-kernel cfg and a unit-stride 3x3 geometry");
-    dm::conv_halo(bp(x), bp(wpack), bp(y), ap, sp, g, c->bn, c->halo_waves, cur_stream(), psc, psh);
-    return;
-  }
-  dm::igemm_fwd(bp(x), bp(wpack), bp(y), ap, sp, g, cfg, cur_stream(), pipe_sched(balance));
-}
-
-// A data gradient as a forward-style GEMM: dy [N,OH,OW,Cout] is the input, dx [N,H,W,Cin] the
-// output, wd the packed weights; the tap grid is filled in per stride below
-dm::ConvGeom dgrad_base(int N, int OH, int OW, int Cout, int H, int W, int Cin, int KH, int KW) {
-  dm::ConvGeom g{};
-  g.N = N; g.H = OH; g.W = OW; g.C = Cout; g.lgC8 = ilog2(Cout / 8);
-  g.OH = H; g.OW = W; g.OC = Cin;
-  g.KW = KW; g.Ncols = Cin; g.wK = KH * KW * Cout;
-  return g;
-}
-
-dm::ConvGeom dgrad_s1_geom(const dm::ConvGeom& base, int KH, int KW, int pad) {
-  auto g = base;
-  g.Hg = g.OH; g.Wg = g.OW; g.isy = 1; g.isx = 1; g.osy = 1; g.osx = 1; g.oy0 = 0; g.ox0 = 0;
-  g.nth = KH; g.ntw = KW; g.dy0 = pad; g.dys = -1; g.dx0 = pad; g.dxs = -1;
-  g.kh0 = 0; g.khs = 1; g.kw0 = 0; g.kws = 1;
-  g.M = (long long)g.N * g.OH * g.OW; g.K = KH * KW * g.C;
-  dm::geom_finalize(g);
-  return g;
-}
-
-// The parity classes of a stride-2 data gradient: class (a, b) writes the output pixels
-// (2y + a, 2x + b), which are disjoint.  The classes go into set a-major and their count is
-// returned; one without pixels or without taps is left out (any_empty: some class has no taps,
-// e.g. the odd pixels of a 1x1/s2 conv, so its pixels are exactly zero)
-int dgrad_s2_classes(const dm::ConvGeom& base, int KH, int KW, int pad, dm::ConvGeomSet& set,
-                     bool& any_empty) {
-  int ng = 0;
-  any_empty = false;
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) {
-      auto g = base;
-      const int kh0 = (a + pad) & 1, kw0 = (b + pad) & 1;
-      const int nth = (KH - kh0 + 1) / 2, ntw = (KW - kw0 + 1) / 2;
-      if (nth <= 0 || ntw <= 0) { any_empty = true; continue; }
-      g.Hg = (g.OH - a + 1) / 2; g.Wg = (g.OW - b + 1) / 2;
-      if (g.Hg <= 0 || g.Wg <= 0) continue;
-      g.isy = 1; g.isx = 1; g.osy = 2; g.osx = 2; g.oy0 = a; g.ox0 = b;
-      g.nth = nth; g.ntw = ntw;
-      g.dy0 = (a + pad - kh0) / 2; g.dys = -1; g.dx0 = (b + pad - kw0) / 2; g.dxs = -1;
-      g.kh0 = kh0; g.khs = 2; g.kw0 = kw0; g.kws = 2;
-      g.M = (long long)g.N * g.Hg * g.Wg; g.K = nth * ntw * g.C;
-      dm::geom_finalize(g);
-      set.g[ng++] = g;
-    }
-  return ng;
-}
-
-// part rows of the classes' single launch with the reduction epilogue (class major, row tile
-// minor; every block writes its row); 0 if cfg has no such launch
-int64_t s2_red_rows(const dm::ConvGeomSet& set, int ng, const dm::ConvCfg& c) {
-  if (!c.multi_merge_red) return 0;
-  long long mmax = 0;
-  for (int i = 0; i < ng; ++i) mmax = std::max(mmax, set.g[i].M);
-  return ng * ((mmax + c.rowtile - 1) / c.rowtile);
+  dm::conv_launch(ops, g, cfg_of(cfg), cur_stream());
 }
 
 // part rows of a stride-2 3x3/p1 data gradient with the reduction epilogue (conv_dgrad red_part)
@@ -267,20 +179,8 @@ int64_t dgrad_s2_red_rows(int64_t N, int64_t H, int64_t W, int64_t cfg) {
   base.N = N; base.OH = H; base.OW = W;
   dm::ConvGeomSet set{};
   bool any_empty;
-  const int ng = dgrad_s2_classes(base, 3, 3, 1, set, any_empty);
-  return s2_red_rows(set, ng, cfg_of(cfg));
-}
-
-// All parity classes in one launch: the pipelined tiles' (blockIdx.y = class), else the igemm
-// tile's (blockIdx.z = class); false when cfg has neither for this geometry
-bool launch_s2(const bf* dy, const bf* wd, bf* dx, const dm::ConvGeomSet& set, int ng,
-               const dm::ConvCfg& c, const bf* add, const dm::DgradSeg2* seg2,
-               const dm::BnBwdRed* red, hipStream_t st, int sched) {
-  if (ng <= 0) return false;
-  if (c.family == dm::ConvFamily::pipe &&
-      dm::conv_pipe_multi(dy, wd, dx, add, set, ng, c.id, st, seg2, red, sched))
-    return true;
-  return dm::igemm_fwd_multi(dy, wd, dx, add, nullptr, set, ng, c.id, st, seg2, red);
+  const int ng = dm::dgrad_classes(base, 3, 3, 2, 1, set, any_empty);
+  return dm::conv_multi_red_rows(set, ng, cfg_of(cfg));
 }
 
 // dx = conv_transpose(dy, w) for stride 1 or 2; add: tensor added to the result (may alias dx
@@ -314,20 +214,22 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
               "wd must be bf16 [Cin][KH][KW][Cout]");
   TORCH_CHECK(stride == 1 || stride == 2, "stride must be 1 or 2");
   const dm::ConvCfg& c = cfg_of(cfg);
-  const int sched = pipe_sched(balance);
-  const bf* addp = nullptr;
-  if (add.has_value()) { need_bf16_nhwc(*add, "add"); TORCH_CHECK(add->sizes() == dx.sizes()); addp = bp(*add); }
-  const bool accumulate = addp != nullptr;
-  TORCH_CHECK(stride == 1 || !accumulate || addp == bp(dx),
+  dm::ConvOperands ops{bp(dy), bp(wd), bp(dx), pipe_sched(balance)};
+  if (add.has_value()) { need_bf16_nhwc(*add, "add"); TORCH_CHECK(add->sizes() == dx.sizes()); ops.add = bp(*add); }
+  const bool accumulate = ops.add != nullptr;
+  TORCH_CHECK(stride == 1 || !accumulate || ops.add == bp(dx),
               "stride-2 dgrad accumulates only in place (add must alias dx)");
   const DeviceGuard guard(dy.device());
   auto st = cur_stream();
-  const dm::ConvGeom base = dgrad_base(N, OH, OW, Cout, H, W, Cin, KH, KW);
+  dm::ConvGeom base;
+  const char* err = dm::dgrad_base_geom(base, N, OH, OW, Cout, H, W, Cin, KH, KW);
+  TORCH_CHECK(!err, err);
   if (add_mask.has_value())
-    TORCH_CHECK(addp && stride == 1 && addp != bp(dx),
+    TORCH_CHECK(ops.add && stride == 1 && ops.add != bp(dx),
                 "add_mask needs a separate add tensor and a stride-1 data gradient");
   const unsigned char* addm = bit_mask(add_mask, dx, "add_mask");
-  // the red_* operands, checked against dx and the launch's part rows
+  // the red_* operands, checked against dx and the launch's part rows, become the launch's
+  dm::BnBwdRed red{};
   auto red_in = [&](int64_t rows) {
     need_bf16_nhwc(*red_y, "red_y");
     TORCH_CHECK(red_y->sizes() == dx.sizes(), "red_y: dx's shape");
@@ -338,34 +240,20 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
     need_f32(*red_mean, "red_mean", Cin);
     need_f32(*red_invstd, "red_invstd", Cin);
     need_f32(*red_part, "red_part", rows * 2 * Cin);
-    return dm::BnBwdRed{bp(*red_y), bit_mask(red_mask, dx, "red_mask"), fp(*red_scale),
-                        fp(*red_shift), fp(*red_mean), fp(*red_invstd), fp(*red_part)};
+    red = dm::BnBwdRed{bp(*red_y), bit_mask(red_mask, dx, "red_mask"), fp(*red_scale),
+                       fp(*red_shift), fp(*red_mean), fp(*red_invstd), fp(*red_part)};
+    ops.red = &red;
   };
-  if (stride == 1) {
-    auto g = dgrad_s1_geom(base, KH, KW, pad);
-    g.addm = addm;
-    if (red_y.has_value()) {
-      const bool pipe = c.family == dm::ConvFamily::pipe && dm::conv_pipe_supported(g, c.id);
-      const bool halo = c.family == dm::ConvFamily::halo && dm::conv_halo_supported(g);
-      TORCH_CHECK(c.red_s1 && (c.family == dm::ConvFamily::res64 || pipe || halo),
-                  "red_*: a cfg whose stride-1 launch has the reduction epilogue "
-                  "(csrc/conv_cfg.h red_s1), on a geometry its kernel covers");
-      const dm::BnBwdRed red = red_in(conv_stats_rows(g.M, cfg));
-      if (pipe)
-        dm::conv_pipe(bp(dy), bp(wd), bp(dx), addp, nullptr, g, c.id, st, &red, sched);
-      else if (halo)
-        dm::conv_halo(bp(dy), bp(wd), bp(dx), addp, nullptr, g, c.bn, c.halo_waves, st, nullptr,
-                      nullptr, &red);
-      else
-        dm::conv_res64(bp(dy), bp(wd), bp(dx), addp, nullptr, g, st, nullptr, nullptr, &red);
-      return;
-    }
-    dm::igemm_fwd(bp(dy), bp(wd), bp(dx), addp, nullptr, g, cfg, st, sched);
-    return;
-  }
   dm::ConvGeomSet set{};
   bool any_empty;
-  const int ng = dgrad_s2_classes(base, KH, KW, pad, set, any_empty);
+  const int ng = dm::dgrad_classes(base, KH, KW, stride, pad, set, any_empty);
+  if (stride == 1) {
+    TORCH_CHECK(ng == 1, "dgrad: empty dx");
+    set.g[0].addm = addm;
+    if (red_y.has_value()) red_in(conv_stats_rows(set.g[0].M, cfg));
+    dm::conv_launch(ops, set.g[0], c, st);
+    return;
+  }
   // a class with no taps is exactly zero, so zero-fill once up front when needed
   if (any_empty && !accumulate)
     TORCH_CHECK(hipMemsetAsync(dx.data_ptr(), 0, dx.numel() * 2, st) == hipSuccess);
@@ -397,22 +285,16 @@ void conv_dgrad(at::Tensor dy, at::Tensor wd, at::Tensor dx, int64_t KH, int64_t
     seg2.w2bytes = (unsigned)(wd2->numel() * 2);
     seg2.C2 = (int)dy2->size(3);
     seg2.z = 0;
+    ops.seg2 = &seg2;
   }
-  dm::BnBwdRed red{};
   if (red_y.has_value()) {
     TORCH_CHECK(c.multi_merge_red && !accumulate && !any_empty && ng == 4,
                 "red_* with stride 2: a complete data gradient (all 4 parity classes, no add) on "
                 "a cfg with a reducing multi-geometry launch (csrc/conv_cfg.h multi_merge_red)");
-    red = red_in(s2_red_rows(set, ng, c));
+    red_in(dm::conv_multi_red_rows(set, ng, c));
   }
-  const bf* acc = accumulate ? bp(dx) : nullptr;
-  const bool special = merged || red_y.has_value();
-  if (launch_s2(bp(dy), bp(wd), bp(dx), set, ng, c, acc, merged ? &seg2 : nullptr,
-                red_y.has_value() ? &red : nullptr, st, sched))
-    return;
-  TORCH_CHECK(!special, "merged / reducing stride-2 dgrad: unsupported cfg / geometry");
-  for (int i = 0; i < ng; ++i)
-    dm::igemm_fwd(bp(dy), bp(wd), bp(dx), acc, nullptr, set.g[i], cfg, st, 0);
+  TORCH_CHECK(dm::conv_launch_multi(ops, set, ng, c, st),
+              "merged / reducing stride-2 dgrad: unsupported cfg / geometry");
 }
 
 // dw (fp32 OIHW [Cout][Cin][KH][KW]) = beta*dw + Σ_m dy ⊗ im2col(x)
@@ -426,29 +308,21 @@ void conv_wgrad(at::Tensor x, at::Tensor dy, at::Tensor dw, at::Tensor slab, int
   need_bf16_nhwc(dy, "dy");
   const int Cout = dy.size(3);
   need_f32(dw, "dw", s2d ? (int64_t)Cout * Cin * 49 : (int64_t)Cout * Cin * KH * KW);
-  auto g = fwd_geom(x, Cout, KH, KW, stride, pad, dy.size(1), dy.size(2));
+  auto g = fwd_geom(x.size(0), x.size(1), x.size(2), x.size(3), Cout, KH, KW, stride, pad,
+                    dy.size(1), dy.size(2));
   TORCH_CHECK(dy.size(0) == x.size(0));
   need_f32(slab, "slab", (int64_t)S * Cout * g.K);
   const long long steps = (g.M + 63) / 64;
   const long long mchunk = ((steps + S - 1) / S) * 64;  // multiple of both kernels' row step
   const DeviceGuard guard(x.device());
   auto st = cur_stream();
+  dm::WgradOperands ops{bp(x), bp(dy), fp(slab), (int)S, mchunk};
   if (pre_scale.has_value()) {
     // x = previous conv's raw output, operand relu(x*sc + sh)
     TORCH_CHECK(pre_shift.has_value() && !s2d, "pre_scale needs pre_shift (not with s2d)");
-    const auto [psc, psh] = pre_bn(pre_scale, pre_shift, x);
-    const dm::WgradCfg* wc = dm::wgrad_cfg((int)cfg);
-    const bool res64 = wc && wc->family == dm::WgradFamily::res64;
-    TORCH_CHECK(wc && wc->pre_bn && (res64 || dm::wgrad_halo_supported(g)),
-                "fused pre-BN needs a wgrad cfg that stages it (csrc/conv_cfg.h pre_bn) and, for "
-                "the halo kernel, a 3x3/s1/p1 geometry");
-    if (res64)
-      dm::wgrad_res64(bp(x), bp(dy), fp(slab), g, (int)S, st, psc, psh);
-    else
-      dm::wgrad_halo(bp(x), bp(dy), fp(slab), g, (int)S, mchunk, wc->taps / 3, st, psc, psh);
-  } else {
-    dm::igemm_wgrad(bp(x), bp(dy), fp(slab), g, (int)S, mchunk, cfg, st);
+    std::tie(ops.pre_sc, ops.pre_sh) = pre_bn(pre_scale, pre_shift, x);
   }
+  dm::wgrad_launch(ops, g, wgrad_cfg_of(cfg), st);
   if (s2d)
     dm::wgrad_reduce_s2d(fp(slab), (int)S, Cout, (int)Cin, g.C, fp(dw), (float)beta, st);
   else
@@ -603,7 +477,9 @@ void bn_apply(at::Tensor y, c10::optional<at::Tensor> res, at::Tensor scale, at:
   need_bf16_nhwc(y, "y");
   need_bf16_nhwc(out, "out");
   const int C = y.size(3);
-  ilog2(C / 8);  // the kernel takes a chunk's channel as i & (C/8 - 1)
+  dm::ConvGeom cg;  // the kernel takes a chunk's channel as i & (C/8 - 1)
+  const char* err = dm::geom_channels(cg, C);
+  TORCH_CHECK(!err, err);
   need_f32(scale, "scale", C);
   need_f32(shift, "shift", C);
   const bf* rp = nullptr;
@@ -1044,6 +920,44 @@ py::object cfg_dict(const Row* c) {
 py::object conv_cfg_info(int64_t cfg) { return cfg_dict(dm::conv_cfg((int)cfg)); }
 py::object wgrad_cfg_info(int64_t cfg) { return cfg_dict(dm::wgrad_cfg((int)cfg)); }
 
+// The kernel a conv over x [N,H,W,C] -> y [.,.,.,Cout] with these operands would run on, as
+// (family, tile, ok): a dry run of the launch entry point, operands standing in for the flags;
+// ok = false: the call is refused.  dgrad: the data gradient; stride 2: the parity classes'
+// launch (tile 0 = one launch per class; `add` plays no part; `merged` = with a projection of
+// dy's own channel count, another count cannot be asked for here); otherwise the forward
+py::tuple conv_route_info(int64_t N, int64_t H, int64_t W, int64_t C, int64_t Cout, int64_t k,
+                          int64_t stride, int64_t pad, int64_t cfg, bool add, bool pre, bool red,
+                          bool dgrad, bool merged) {
+  const int OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
+  dm::ConvGeom g;
+  const char* err = dgrad ? dm::dgrad_base_geom(g, N, OH, OW, Cout, H, W, C, k, k)
+                          : dm::conv_fwd_geom(g, N, H, W, C, Cout, k, k, stride, pad, OH, OW);
+  TORCH_CHECK(!err, err);
+  const bf b{};
+  const float f{};
+  const dm::BnBwdRed rd{};
+  const dm::DgradSeg2 s2{nullptr, nullptr, 0, 0, g.C, 0};
+  const dm::ConvOperands ops{nullptr, nullptr, nullptr, dm::kPipeAuto, add ? &b : nullptr, nullptr,
+                             pre ? &f : nullptr, pre ? &f : nullptr, red ? &rd : nullptr,
+                             merged ? &s2 : nullptr};
+  dm::ConvRoute r{};
+  dm::ConvGeomSet set{};
+  bool any_empty;
+  const int ng = dgrad ? dm::dgrad_classes(g, k, k, stride, pad, set, any_empty) : 0;
+  if (dgrad && stride == 2) dm::conv_launch_multi(ops, set, ng, cfg_of(cfg), nullptr, &r);
+  else dm::conv_launch(ops, dgrad ? set.g[0] : g, cfg_of(cfg), nullptr, &r);
+  return py::make_tuple(dm::family_name(r.kernel), r.tile, r.ok);
+}
+py::tuple wgrad_route_info(int64_t N, int64_t H, int64_t W, int64_t C, int64_t Cout, int64_t k,
+                           int64_t stride, int64_t pad, int64_t cfg, bool pre) {
+  const int OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
+  const float f{};
+  dm::WgradRoute r{};
+  dm::wgrad_launch({nullptr, nullptr, nullptr, 1, 64, pre ? &f : nullptr, pre ? &f : nullptr},
+                   fwd_geom(N, H, W, C, Cout, k, k, stride, pad, OH, OW), wgrad_cfg_of(cfg), nullptr, &r);
+  return py::make_tuple(dm::family_name(r.kernel), r.tile, r.ok);
+}
+
 void register_resnet(pybind11::module_& m) {
   m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("wpack"), py::arg("y"), py::arg("stats"),
         py::arg("add"), py::arg("KH"), py::arg("KW"), py::arg("stride"), py::arg("pad"),
@@ -1056,6 +970,13 @@ void register_resnet(pybind11::module_& m) {
         py::arg("M"), py::arg("cfg"), py::arg("ncols") = -1);
   m.def("conv_cfg_info", &conv_cfg_info, py::arg("cfg"));
   m.def("wgrad_cfg_info", &wgrad_cfg_info, py::arg("cfg"));
+  m.def("conv_route_info", &conv_route_info, py::arg("N"), py::arg("H"), py::arg("W"), py::arg("C"),
+        py::arg("Cout"), py::arg("k"), py::arg("stride"), py::arg("pad"), py::arg("cfg"),
+        py::arg("add") = false, py::arg("pre") = false, py::arg("red") = false,
+        py::arg("dgrad") = false, py::arg("merged") = false);
+  m.def("wgrad_route_info", &wgrad_route_info, py::arg("N"), py::arg("H"), py::arg("W"),
+        py::arg("C"), py::arg("Cout"), py::arg("k"), py::arg("stride"), py::arg("pad"),
+        py::arg("cfg"), py::arg("pre") = false);
   m.def("conv_dgrad", &conv_dgrad, py::arg("dy"), py::arg("wd"), py::arg("dx"), py::arg("KH"),
         py::arg("KW"), py::arg("stride"), py::arg("pad"),
         py::arg("add") = py::none(), py::arg("cfg") = 12, py::arg("add_mask") = py::none(),

@@ -1,8 +1,11 @@
 // The conv kernel configs: what every forward-style `cfg` and weight-gradient `cfg` id is and
-// can do, in one table each.  Host-only plain C++17 (no HIP, no torch): the launchers, the
-// bindings and (through conv_cfg_info / wgrad_cfg_info) the Python layer read it, and
-// tests/native/cfg_table.cpp checks and prints it.  Adding or removing a kernel = one row here
-// plus its launcher.  Which id a layer gets is policy and lives in dmlab/ops/convbn.py.
+// can do, in one table each, and the routing rule (conv_route / conv_route_multi / wgrad_route):
+// which kernel a call with these operands runs on.  Host-only plain C++17 (no HIP, no torch):
+// the dispatcher (conv_launch.cpp), the launchers, the bindings and (through conv_cfg_info /
+// wgrad_cfg_info) the Python layer read it; tests/native/cfg_table.cpp checks and prints the
+// tables and tests/native/conv_route.cpp the routes.  Adding a kernel = one row, one launcher,
+// one line in the dispatcher.  Which id a layer gets is policy and lives in
+// dmlab/ops/convbn.py.
 #pragma once
 #include <cstddef>
 #include <type_traits>
@@ -133,12 +136,64 @@ constexpr int cfg_fallback(const Row& c, int ncols) {
   return ncols % 128 == 0 ? c.fallback128 : c.fallback;
 }
 
+// ---- routing: the kernel a launch runs on.  `fits` is the answer of the routed row's own
+// *_supported(geometry) predicate (they stay with their kernels' constants); everything else is
+// decided here.  kernel + tile name what runs: an igemm / v2 tile id, or the row of the
+// specialised kernel; ok = false: the call is refused.
+struct ConvRoute { ConvFamily kernel; int tile; bool ok; };
+struct WgradRoute { WgradFamily kernel; int tile; bool ok; };
+
+// One geometry: forward, stride-1 dgrad, one parity class.  add / pre / red: the launch has an
+// ADD operand / a fused pre-BN operand / the BN-backward reduction (RED) epilogue.  A tile that
+// takes no fused pre-BN names the one (same statistics slab rows) that does: with pre, the row
+// is first replaced by its pre_reroute, and `fits` is that row's
+constexpr ConvRoute conv_route(const ConvCfg& c0, bool fits, bool add, bool pre, bool red,
+                               int ncols) {
+  const ConvCfg& c = pre && c0.pre_reroute ? *conv_cfg(c0.pre_reroute) : c0;
+  const ConvFamily f = c.family;
+  const bool res64 = f == ConvFamily::res64;
+  const ConvRoute own{f, c.id, true}, refuse{f, c.id, false};
+  if (pre || red) {  // no fallback tile stages a pre-BN operand or reduces; never both at once
+    const bool has = res64 || f == ConvFamily::halo || (red && f == ConvFamily::pipe);
+    return !(pre && red) && (pre ? c.pre_bn : c.red_s1) && has && fits ? own : refuse;
+  }
+  // its own kernel where it fits (the stem takes no ADD); else the fallback tile, res64 has none
+  if (f == ConvFamily::igemm || (fits && !(add && f == ConvFamily::stem))) return own;
+  return res64 ? refuse : ConvRoute{ConvFamily::igemm, cfg_fallback(c, ncols), true};
+}
+
+// The parity classes of a stride-2 dgrad in one launch.  fits_all: every class fits; seg2: a
+// merged projection segment, seg2_same_c: of the operand's channel count; red: RED epilogue.
+// tile kPerClass = no single launch: one conv_route launch per class instead
+constexpr int kPerClass = 0;
+constexpr ConvRoute conv_route_multi(const ConvCfg& c, bool fits_all, bool seg2, bool seg2_same_c,
+                                     bool red) {
+  const bool special = seg2 || red;
+  const bool single = c.family == ConvFamily::pipe ? fits_all && (!seg2 || seg2_same_c)
+                      : c.family == ConvFamily::igemm && (c.multi_merge_red || (c.multi && !special));
+  return single ? ConvRoute{c.family, c.id, true} : ConvRoute{c.family, kPerClass, !special};
+}
+
+constexpr WgradRoute wgrad_route(const WgradCfg& c, bool fits, bool pre, int ncols) {
+  const WgradFamily f = c.family;
+  const WgradRoute own{f, c.id, true}, refuse{f, c.id, false};
+  const bool res64 = f == WgradFamily::res64;
+  if (pre)  // no fallback tile stages a pre-BN operand
+    return c.pre_bn && (res64 || f == WgradFamily::halo) && fits ? own : refuse;
+  if (f == WgradFamily::v2 || fits) return own;
+  return res64 ? refuse : WgradRoute{WgradFamily::v2, cfg_fallback(c, ncols), true};
+}
+
+constexpr const char* kConvFamilyNames[] = {"igemm", "halo", "stem", "res64", "pipe"};
+constexpr const char* kWgradFamilyNames[] = {"v2", "halo", "s2", "res64"};
+constexpr const char* family_name(ConvFamily f) { return kConvFamilyNames[(int)f]; }
+constexpr const char* family_name(WgradFamily f) { return kWgradFamilyNames[(int)f]; }
+
 // Every field of a row as f(name, value), value a const char*, int or bool: the one list behind
 // the conv_cfg_info / wgrad_cfg_info dicts and the lines tests/native/cfg_table.cpp prints
 template <class F>
 void cfg_fields(const ConvCfg& c, F&& f) {
-  constexpr const char* fam[] = {"igemm", "halo", "stem", "res64", "pipe"};
-  f("id", c.id); f("family", fam[(int)c.family]);
+  f("id", c.id); f("family", family_name(c.family));
   f("bm", c.bm); f("bn", c.bn); f("wm", c.wm); f("wn", c.wn); f("mf32", c.mf32);
   f("depth", c.depth); f("minw", c.minw); f("halo_waves", c.halo_waves);
   f("rowtile", c.rowtile); f("fallback", c.fallback); f("fallback128", c.fallback128);
@@ -148,8 +203,7 @@ void cfg_fields(const ConvCfg& c, F&& f) {
 }
 template <class F>
 void cfg_fields(const WgradCfg& c, F&& f) {
-  constexpr const char* fam[] = {"v2", "halo", "s2", "res64"};
-  f("id", c.id); f("family", fam[(int)c.family]);
+  f("id", c.id); f("family", family_name(c.family));
   f("bm", c.bm); f("bk", c.bk); f("taps", c.taps); f("pre_bn", c.pre_bn);
   f("fallback", c.fallback); f("fallback128", c.fallback128);
 }

@@ -25,7 +25,6 @@
 // parity classes of stride-2 dgrad (their dY grid is the launch grid, taps are unit-
 // stride).  MFMA v_mfma_f32_32x32x16_bf16, 4 waves each owning 64 x BN/2.
 #include "common.h"
-#include "conv_geom.h"
 #include "igemm_common.h"
 #include "kernels.h"
 
@@ -309,9 +308,7 @@ int halo_rows_needed(const ConvGeom& g, int bm = HBM) {
 }
 
 template <int BN, int HR, int WM, int WN, int BMH = HBM, int PF = 1, bool RED = false>
-void launch_halo(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-                 const ConvGeom& g, const float* pre_sc, const float* pre_sh, hipStream_t st,
-                 const BnBwdRed* red = nullptr) {
+void launch_halo(const ConvOperands& o, const ConvGeom& g, hipStream_t st) {
   constexpr int RPP = WM * WN * 8;
   const size_t main = (size_t)(RPP * HR + 1) * HBK * 2 + (size_t)2 * BN * HBK * 2 + MAXTAPS * 16;
   const size_t epi = (size_t)128 * (BN + 4) * 4;  // staged in 128-row bands
@@ -320,21 +317,21 @@ void launch_halo(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD
   const unsigned xb = (unsigned)((long long)g.N * g.H * g.W * g.C * 2);
   const unsigned wb = (unsigned)((long long)g.Ncols * g.wK * 2);
   auto k = RED ? conv_halo_kernel<BN, HR, WM, WN, BMH, false, PF, RED>
-         : pre_sc ? conv_halo_kernel<BN, HR, WM, WN, BMH, true, PF>
-                  : conv_halo_kernel<BN, HR, WM, WN, BMH, false, PF>;
-  const BnBwdRed rarg = red ? *red : BnBwdRed{};
+         : o.pre_sc ? conv_halo_kernel<BN, HR, WM, WN, BMH, true, PF>
+                    : conv_halo_kernel<BN, HR, WM, WN, BMH, false, PF>;
+  const BnBwdRed rarg = o.red ? *o.red : BnBwdRed{};
   set_smem_attr(k, sm);
   // XCD-aware 1-D grid over the M tiles (padded to a multiple of 8) x N tiles: the N tiles of
   // one M tile share an XCD's L2.  Measured (tools/bench_conv.py, batch 512): layer3 fwd
   // 845 -> 880 TF/s, dgrad 859 -> 892; layer2 / layer4 +2-7 %
   if (nt > 1) {
     const unsigned mt8 = (mt + 7) / 8 * 8;
-    k<<<dim3(mt8 * nt), WM * WN * 64, sm, st>>>(X, Wp, Y, ADD, stats, g, xb, wb, pre_sc, pre_sh,
-                                                (int)nt, (int)mt, rarg);
+    k<<<dim3(mt8 * nt), WM * WN * 64, sm, st>>>(o.X, o.Wp, o.Y, o.add, o.stats, g, xb, wb,
+                                                o.pre_sc, o.pre_sh, (int)nt, (int)mt, rarg);
     return;
   }
-  k<<<dim3(mt, nt), WM * WN * 64, sm, st>>>(X, Wp, Y, ADD, stats, g, xb, wb, pre_sc, pre_sh,
-                                            0, (int)mt, rarg);
+  k<<<dim3(mt, nt), WM * WN * 64, sm, st>>>(o.X, o.Wp, o.Y, o.add, o.stats, g, xb, wb, o.pre_sc,
+                                            o.pre_sh, 0, (int)mt, rarg);
 }
 }  // namespace
 
@@ -350,39 +347,35 @@ bool conv_halo_supported(const ConvGeom& g) {
   return halo_rows_needed(g) <= 32 * 12 && halo_rows_needed(g, 256) <= 32 * 14;
 }
 
-// tiles (igemm_fwd's halo cfgs): waves 4 | 0x100 = 128 px as 2 x 2 waves of 64 x 64 with two
-// weight tiles of register prefetch (cfg 42); 16 = 256 px as 4 x 2 waves of 64 x 32 (cfg 39);
-// 32 = 256 px as 4 x 1 waves of 64 x 64 (cfg 41)
-void conv_halo(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-               const ConvGeom& g, int bn, int waves, hipStream_t st, const float* pre_sc,
-               const float* pre_sh, const BnBwdRed* red) {
+// tiles (the row's halo_waves): 4 | 0x100 = 128 px as 2 x 2 waves of 64 x 64 with two weight
+// tiles of register prefetch (cfg 42); 16 = 256 px as 4 x 2 waves of 64 x 32 (cfg 39); 32 =
+// 256 px as 4 x 1 waves of 64 x 64 (cfg 41)
+void conv_halo(const ConvOperands& o, const ConvGeom& g, const ConvCfg& cfg, hipStream_t st) {
+  const int bn = cfg.bn, waves = cfg.halo_waves;
   const int hp = halo_rows_needed(g), hp2 = halo_rows_needed(g, 256);
-  if (red) {
+  if (o.red) {
     // the BN-backward reduction epilogue is built for the cfg 42 tile (layer2's data gradient)
-    if (waves != (4 | 0x100) || bn != 128 || pre_sc)
+    if (waves != (4 | 0x100) || bn != 128 || o.pre_sc)
       throw std::runtime_error("conv_halo: BN-backward reduction needs cfg 42, no PRE input");
     const int hr = hp <= 192 ? 6 : hp <= 256 ? 8 : 12;
-    if (hr == 6) launch_halo<128, 6, 2, 2, HBM, 2, true>(X, Wp, Y, ADD, stats, g, nullptr, nullptr, st, red);
-    else if (hr == 8) launch_halo<128, 8, 2, 2, HBM, 2, true>(X, Wp, Y, ADD, stats, g, nullptr, nullptr, st, red);
-    else launch_halo<128, 12, 2, 2, HBM, 2, true>(X, Wp, Y, ADD, stats, g, nullptr, nullptr, st, red);
-    DM_CHECK(hipGetLastError());
-    return;
-  }
-  if (waves == (4 | 0x100) && bn == 128) {
+    if (hr == 6) launch_halo<128, 6, 2, 2, HBM, 2, true>(o, g, st);
+    else if (hr == 8) launch_halo<128, 8, 2, 2, HBM, 2, true>(o, g, st);
+    else launch_halo<128, 12, 2, 2, HBM, 2, true>(o, g, st);
+  } else if (waves == (4 | 0x100) && bn == 128) {
     const int hr = hp <= 192 ? 6 : hp <= 256 ? 8 : 12;
-    if (hr == 6) launch_halo<128, 6, 2, 2, HBM, 2>(X, Wp, Y, ADD, stats, g, pre_sc, pre_sh, st);
-    else if (hr == 8) launch_halo<128, 8, 2, 2, HBM, 2>(X, Wp, Y, ADD, stats, g, pre_sc, pre_sh, st);
-    else launch_halo<128, 12, 2, 2, HBM, 2>(X, Wp, Y, ADD, stats, g, pre_sc, pre_sh, st);
+    if (hr == 6) launch_halo<128, 6, 2, 2, HBM, 2>(o, g, st);
+    else if (hr == 8) launch_halo<128, 8, 2, 2, HBM, 2>(o, g, st);
+    else launch_halo<128, 12, 2, 2, HBM, 2>(o, g, st);
   } else if (waves == 16 && bn == 64) {
     const int hr = (hp2 + 63) / 64;
-    if (hr <= 5) launch_halo<64, 5, 4, 2, 256>(X, Wp, Y, ADD, stats, g, pre_sc, pre_sh, st);
-    else if (hr <= 6) launch_halo<64, 6, 4, 2, 256>(X, Wp, Y, ADD, stats, g, pre_sc, pre_sh, st);
-    else launch_halo<64, 7, 4, 2, 256>(X, Wp, Y, ADD, stats, g, pre_sc, pre_sh, st);
+    if (hr <= 5) launch_halo<64, 5, 4, 2, 256>(o, g, st);
+    else if (hr <= 6) launch_halo<64, 6, 4, 2, 256>(o, g, st);
+    else launch_halo<64, 7, 4, 2, 256>(o, g, st);
   } else if (waves == 32 && bn == 64) {
     const int hr = (hp2 + 31) / 32;
-    if (hr <= 10) launch_halo<64, 10, 4, 1, 256>(X, Wp, Y, ADD, stats, g, pre_sc, pre_sh, st);
-    else if (hr <= 12) launch_halo<64, 12, 4, 1, 256>(X, Wp, Y, ADD, stats, g, pre_sc, pre_sh, st);
-    else launch_halo<64, 14, 4, 1, 256>(X, Wp, Y, ADD, stats, g, pre_sc, pre_sh, st);
+    if (hr <= 10) launch_halo<64, 10, 4, 1, 256>(o, g, st);
+    else if (hr <= 12) launch_halo<64, 12, 4, 1, 256>(o, g, st);
+    else launch_halo<64, 14, 4, 1, 256>(o, g, st);
   } else {
     throw std::runtime_error("conv_halo: unknown tile (cfg 39 / 41 / 42)");
   }

@@ -22,14 +22,12 @@
 // reduces per-channel Σy and Σy² (BatchNorm batch statistics) from the fp32
 // accumulators into a per-row-tile slab — BN statistics cost no extra pass over Y.
 //
-// Weight gradient (igemm_wgrad): dW[co, tap, ci] = Σ_m dY[m, co] · X_im2col[m, (tap, ci)]
+// Weight gradient (igemm_wgrad2_kernel): dW[co, tap, ci] = Σ_m dY[m, co] · X_im2col[m, (tap, ci)]
 // reduces over m, which is the row index of both operands in memory, so both tiles
 // are staged [m][cols] and read with the CDNA4 transpose read ds_read_b64_tr_b16.
 // The reduction is split over blocks into fp32 slabs and combined by a fixed-order
 // reduce that also permutes to the OIHW fp32 gradient layout and applies beta.
 #include "common.h"
-#include "conv_cfg.h"
-#include "conv_geom.h"
 #include "igemm_common.h"
 #include "kernels.h"
 
@@ -702,94 +700,52 @@ void wgrad_reduce_s2d(const float* slab, int S, int Cout, int C, int Cp, float* 
 }
 
 // ------------------------------------------------------------------ launchers
-static size_t fwd_smem(int BM, int BN) {
-  const size_t main = (size_t)2 * (BM + BN) * 64 * 2 + MAXTAPS * 16;
-  const size_t epi = (size_t)BM * (BN + 4) * 4;
-  return main > epi ? main : epi;
-}
-
-template <int BM, int BN, int WM, int WN, bool MF32, int DEPTH, bool SEG2 = false, bool RED = false>
-static void launch_fwd3_set(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
-                            float* stats, const ConvGeomSet& gs, int ng, hipStream_t st,
-                            const DgradSeg2* seg2 = nullptr, const BnBwdRed* red = nullptr) {
+// kConvCfgs[I] of an igemm row: igemm_fwd3_kernel's template arguments come from the table
+template <size_t I, bool SEG2 = false, bool RED = false>
+static void launch_fwd3_row(const ConvOperands& o, const ConvGeomSet& gs, int ng, hipStream_t st) {
+  constexpr ConvCfg c = kConvCfgs[I];
   const ConvGeom& g = gs.g[0];
   long long mmax = 0;
   for (int i = 0; i < ng; ++i) mmax = gs.g[i].M > mmax ? gs.g[i].M : mmax;
-  const size_t sm = fwd_smem(BM, BN);
-  dim3 grid((unsigned)((mmax + BM - 1) / BM), (g.Ncols + BN - 1) / BN, ng);
+  const size_t main = (size_t)2 * (c.bm + c.bn) * 64 * 2 + MAXTAPS * 16;
+  const size_t epi = (size_t)c.bm * (c.bn + 4) * 4, sm = main > epi ? main : epi;
+  dim3 grid((unsigned)((mmax + c.bm - 1) / c.bm), (g.Ncols + c.bn - 1) / c.bn, ng);
   const unsigned xb = (unsigned)((long long)g.N * g.H * g.W * g.C * 2);
   const unsigned wb = (unsigned)((long long)g.Ncols * g.wK * 2);
-  const DgradSeg2 s2 = seg2 ? *seg2 : DgradSeg2{};
-  const BnBwdRed rd = red ? *red : BnBwdRed{};
-  auto k = igemm_fwd3_kernel<BM, BN, WM, WN, MF32, DEPTH, SEG2, RED>;
+  const DgradSeg2 s2 = o.seg2 ? *o.seg2 : DgradSeg2{};
+  const BnBwdRed rd = o.red ? *o.red : BnBwdRed{};
+  auto k = igemm_fwd3_kernel<c.bm, c.bn, c.wm, c.wn, c.mf32, c.depth, SEG2, RED>;
   set_smem_attr(k, sm);
-  k<<<grid, WM * WN * 64, sm, st>>>(X, Wp, Y, ADD, stats, gs, xb, wb, s2, rd);
+  k<<<grid, c.wm * c.wn * 64, sm, st>>>(o.X, o.Wp, o.Y, o.add, o.stats, gs, xb, wb, s2, rd);
 }
 
-// kConvCfgs[I] of an igemm row: igemm_fwd3_kernel's template arguments come from the table
-template <size_t I, bool SEG2 = false, bool RED = false>
-static void launch_fwd3_row(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
-                            float* stats, const ConvGeomSet& gs, int ng, hipStream_t st,
-                            const DgradSeg2* seg2 = nullptr, const BnBwdRed* red = nullptr) {
-  constexpr ConvCfg c = kConvCfgs[I];
-  launch_fwd3_set<c.bm, c.bn, c.wm, c.wn, c.mf32, c.depth, SEG2, RED>(X, Wp, Y, ADD, stats, gs, ng,
-                                                                       st, seg2, red);
-}
-
-// up to four geometries sharing X / W / Y (the parity classes of a stride-2 dgrad) in one
-// launch of a tile that has one (no statistics: the classes' row tiles would collide).  The
-// merged-segment / reduction-epilogue variants exist only for the rows that say so
-bool igemm_fwd_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-                     const ConvGeomSet& gs, int ng, int cfg, hipStream_t st, const DgradSeg2* seg2,
-                     const BnBwdRed* red) {
-  if (seg2 && (seg2->C2 % 64 != 0 || seg2->z < 0 || seg2->z >= ng))
-    throw std::runtime_error("igemm_fwd_multi: seg2 needs C2 % 64 == 0 and a valid geometry");
+// One launch of an igemm tile over ng geometries sharing X / W / Y (statistics only with one:
+// the classes' row tiles would collide).  The merged-segment / reduction-epilogue variants
+// exist only for the rows that say so (the dispatcher asks for no other)
+void igemm_tile(const ConvOperands& o, const ConvGeomSet& gs, int ng, const ConvCfg& cfg,
+                hipStream_t st) {
+  if (o.seg2 && (o.seg2->C2 % 64 != 0 || o.seg2->z < 0 || o.seg2->z >= ng))
+    throw std::runtime_error("igemm_tile: seg2 needs C2 % 64 == 0 and a valid geometry");
+  // Two walks on purpose: the compiler emits kernels in instantiation order, and this order
+  // (the merge / RED rows with all their variants first, then the plain launch of the other
+  // rows) keeps the device code object byte-identical to the one this layout replaced.  One
+  // merged walk computes the same but reorders the kernels in the object
   bool done = false;
-  with_cfg_row<kConvCfgs, ConvFamily::igemm>(cfg, [&](auto row) {
+  with_cfg_row<kConvCfgs, ConvFamily::igemm>(cfg.id, [&](auto row) {
     constexpr size_t I = decltype(row)::value;
     if constexpr (kConvCfgs[I].multi_merge_red) {
-      if (seg2 && red) launch_fwd3_row<I, true, true>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red);
-      else if (seg2) launch_fwd3_row<I, true, false>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red);
-      else if (red) launch_fwd3_row<I, false, true>(X, Wp, Y, ADD, stats, gs, ng, st, seg2, red);
-      else launch_fwd3_row<I>(X, Wp, Y, ADD, stats, gs, ng, st);
+      if (o.seg2 && o.red) launch_fwd3_row<I, true, true>(o, gs, ng, st);
+      else if (o.seg2) launch_fwd3_row<I, true, false>(o, gs, ng, st);
+      else if (o.red) launch_fwd3_row<I, false, true>(o, gs, ng, st);
+      else launch_fwd3_row<I>(o, gs, ng, st);
       done = true;
-    } else if constexpr (kConvCfgs[I].multi) {
-      if (!seg2 && !red) {
-        launch_fwd3_row<I>(X, Wp, Y, ADD, stats, gs, ng, st);
-        done = true;
-      }
     }
   });
-  return done;
-}
-
-// Forward-style conv GEMM (forward, stride-1 dgrad, one dgrad parity class) on the kernel
-// conv_cfg.h lists for cfg.  A geometry the specialised kernel does not cover runs on the row's
-// fallback igemm tile, which has the same row tile, so the statistics slab rows still match.
-void igemm_fwd(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-               const ConvGeom& g, int cfg, hipStream_t st, int pipe_sched) {
-  const ConvCfg* c = conv_cfg(cfg);
-  if (!c) throw std::runtime_error("igemm_fwd: unknown cfg " + std::to_string(cfg));
-  switch (c->family) {
-    case ConvFamily::pipe:
-      if (conv_pipe_supported(g, cfg)) return conv_pipe(X, Wp, Y, ADD, stats, g, cfg, st, nullptr, pipe_sched);
-      break;
-    case ConvFamily::res64:
-      return conv_res64(X, Wp, Y, ADD, stats, g, st);  // throws if unsupported
-    case ConvFamily::stem:
-      if (!ADD && stem_conv_supported(g)) return stem_conv(X, Wp, Y, stats, g, st);
-      break;
-    case ConvFamily::halo:
-      if (conv_halo_supported(g))
-        return conv_halo(X, Wp, Y, ADD, stats, g, c->bn, c->halo_waves, st);
-      break;
-    case ConvFamily::igemm:
-      break;
-  }
-  const int tile = c->family == ConvFamily::igemm ? cfg : cfg_fallback(*c, g.Ncols);
-  with_cfg_row<kConvCfgs, ConvFamily::igemm>(tile, [&](auto row) {
-    launch_fwd3_row<decltype(row)::value>(X, Wp, Y, ADD, stats, ConvGeomSet::one(g), 1, st);
-  });
+  if (!done && !o.seg2 && !o.red)  // a row without the variants
+    done = with_cfg_row<kConvCfgs, ConvFamily::igemm>(cfg.id, [&](auto row) {
+      launch_fwd3_row<decltype(row)::value>(o, gs, ng, st);
+    });
+  if (!done) throw std::runtime_error("igemm_tile: no such launch of cfg " + std::to_string(cfg.id));
 }
 
 template <int BM, int BK>
@@ -804,29 +760,14 @@ static void launch_wgrad2(const bf16_t* X, const bf16_t* DY, float* slab, const 
   k<<<grid, 256, sm, st>>>(X, DY, slab, g, mchunk, xb, db);
 }
 
-// Weight gradient on the kernel conv_cfg.h lists for cfg; a geometry the halo / stride-2
-// kernel does not cover runs on the row's fallback v2 tile
-void igemm_wgrad(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
-                 long long mchunk, int cfg, hipStream_t st) {
-  const WgradCfg* c = wgrad_cfg(cfg);
-  if (!c) throw std::runtime_error("igemm_wgrad: unknown cfg " + std::to_string(cfg));
-  switch (c->family) {
-    case WgradFamily::res64:
-      return wgrad_res64(X, DY, slab, g, S, st);  // throws if unsupported
-    case WgradFamily::s2:
-      if (wgrad_s2_supported(g)) return wgrad_s2(X, DY, slab, g, S, mchunk, st);
-      break;
-    case WgradFamily::halo:
-      if (wgrad_halo_supported(g)) return wgrad_halo(X, DY, slab, g, S, mchunk, c->taps / 3, st);
-      break;
-    case WgradFamily::v2:
-      break;
-  }
-  const int tile = c->family == WgradFamily::v2 ? cfg : cfg_fallback(*c, g.Ncols);
-  with_cfg_row<kWgradCfgs, WgradFamily::v2>(tile, [&](auto row) {
+// One launch of a v2 weight-gradient tile
+void wgrad_tile(const WgradOperands& o, const ConvGeom& g, const WgradCfg& cfg, hipStream_t st) {
+  const auto launch = [&](auto row) {
     constexpr WgradCfg t = kWgradCfgs[decltype(row)::value];
-    launch_wgrad2<t.bm, t.bk>(X, DY, slab, g, S, mchunk, st);
-  });
+    launch_wgrad2<t.bm, t.bk>(o.X, o.DY, o.slab, g, o.S, o.mchunk, st);
+  };
+  if (!with_cfg_row<kWgradCfgs, WgradFamily::v2>(cfg.id, launch))
+    throw std::runtime_error("wgrad_tile: not a v2 tile");
 }
 
 void wgrad_reduce(const float* slab, int S, int Cout, int C, int Cin, int KH, int KW, float* dw,

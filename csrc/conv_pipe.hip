@@ -30,8 +30,6 @@
 // swz), conflict-free for the 32x32x16 fragment reads; the DMA image is lane-linear (base +
 // 16 * lane), so the swizzle is applied to the SOURCE chunk each lane fetches.
 #include "common.h"
-#include "conv_cfg.h"
-#include "conv_geom.h"
 #include "conv_pipe_plan.h"
 #include "igemm_common.h"
 #include "kernels.h"
@@ -651,25 +649,12 @@ __global__ void __launch_bounds__(WM * WN * 64, MINW) conv_pipe_bal_kernel(
 
 PipeWorkspaceFn g_pipe_ws = nullptr;
 
-// workgroups resident at one per CU: the balanced grid never exceeds it
-int pipe_cu_count() {
-  static int cus[64] = {};
-  int dev = 0;
-  DM_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return 0;
-  if (!cus[dev])
-    DM_CHECK(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
-  return cus[dev];
-}
-
 template <int BN, int WM, int WN, int MINW>
-void launch_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-                 const ConvGeomSet& gs, int ng, hipStream_t st, const BnBwdRed* red = nullptr,
-                 const DgradSeg2* seg2 = nullptr, int sched = 0) {
+void launch_pipe(const ConvOperands& o, const ConvGeomSet& gs, int ng, hipStream_t st) {
   const ConvGeom& g = gs.g[0];
   constexpr size_t STG = (size_t)PBM * PBK * 2 + (size_t)BN * PBK * 2;
   const size_t sm_main = 2 * STG;
-  const size_t sm_epi = (size_t)WM * WN * 32 * (BN / WN + 4) * 4 + (red ? (size_t)WM * BN * 8 : 0);
+  const size_t sm_epi = (size_t)WM * WN * 32 * (BN / WN + 4) * 4 + (o.red ? (size_t)WM * BN * 8 : 0);
   const size_t sm = sm_main > sm_epi ? sm_main : sm_epi;
   long long mmax = 0;
   for (int i = 0; i < ng; ++i) mmax = gs.g[i].M > mmax ? gs.g[i].M : mmax;
@@ -677,36 +662,36 @@ void launch_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD
   const int ntN = (g.Ncols + BN - 1) / BN;
   const unsigned xb = (unsigned)((long long)g.N * g.H * g.W * g.C * 2);
   const unsigned wb = (unsigned)((long long)g.Ncols * g.wK * 2);
-  if (seg2 && (seg2->C2 != g.C || seg2->z < 0 || seg2->z >= ng))
+  if (o.seg2 && (o.seg2->C2 != g.C || o.seg2->z < 0 || o.seg2->z >= ng))
     throw std::runtime_error("conv_pipe: the merged segment needs X's channel count");
-  auto k = red ? (seg2 ? conv_pipe_kernel<BN, WM, WN, MINW, true, true>
-                       : conv_pipe_kernel<BN, WM, WN, MINW, true, false>)
-               : (seg2 ? conv_pipe_kernel<BN, WM, WN, MINW, false, true>
-                       : conv_pipe_kernel<BN, WM, WN, MINW, false, false>);
-  const BnBwdRed rarg = red ? *red : BnBwdRed{};
-  const DgradSeg2 sarg = seg2 ? *seg2 : DgradSeg2{};
+  auto k = o.red ? (o.seg2 ? conv_pipe_kernel<BN, WM, WN, MINW, true, true>
+                           : conv_pipe_kernel<BN, WM, WN, MINW, true, false>)
+                 : (o.seg2 ? conv_pipe_kernel<BN, WM, WN, MINW, false, true>
+                           : conv_pipe_kernel<BN, WM, WN, MINW, false, false>);
+  const BnBwdRed rarg = o.red ? *o.red : BnBwdRed{};
+  const DgradSeg2 sarg = o.seg2 ? *o.seg2 : DgradSeg2{};
   constexpr int NT = WM * WN * 64;
   // the balanced schedule (conv_pipe_plan.h; cfg 90's tile only): forced by sched > 0 wherever
   // it is eligible, else when the model says it wins.  A capturing stream keeps the
   // data-parallel launch: the sequence number is a kernel argument, frozen under replay
   if constexpr (BN == 256 && WM == 2 && WN == 4 && MINW == 1) {
-    if (sched != 0 && g_pipe_ws) {
-      const int ncu = pipe_cu_count();
-      const int G = sched > 0 ? sched : ncu;
+    if (o.sched != 0 && g_pipe_ws) {
+      const int ncu = device_cu_count();  // one workgroup per CU: the balanced grid's limit
+      const int G = o.sched > 0 ? o.sched : ncu;
       const long long T = (long long)mtiles * ntN;
       const int S = g.nth * g.ntw * (g.C / PBK);
       hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      if (G <= ncu && pipe_balanced_eligible(T, S, G, ng, seg2 != nullptr) &&
-          (sched > 0 || pipe_balanced_wins(T, S, G)) &&
+      if (G <= ncu && pipe_balanced_eligible(T, S, G, ng, o.seg2 != nullptr) &&
+          (o.sched > 0 || pipe_balanced_wins(T, S, G)) &&
           hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
         const PipeWorkspace ws = g_pipe_ws(st, ncu);
         if (ws.slots && ws.cap >= G) {
-          auto kb = red ? conv_pipe_bal_kernel<BN, WM, WN, MINW, true>
-                        : conv_pipe_bal_kernel<BN, WM, WN, MINW, false>;
+          auto kb = o.red ? conv_pipe_bal_kernel<BN, WM, WN, MINW, true>
+                          : conv_pipe_bal_kernel<BN, WM, WN, MINW, false>;
           set_smem_attr(kb, sm);
-          kb<<<dim3((unsigned)G), NT, sm, st>>>(X, Wp, Y, ADD, stats, g, xb, wb, ntN, S, T * S / G,
-                                                (int)(T * S % G), ws.slots, ws.flags, ws.timeout,
-                                                ws.seq, rarg);
+          kb<<<dim3((unsigned)G), NT, sm, st>>>(o.X, o.Wp, o.Y, o.add, o.stats, g, xb, wb, ntN, S,
+                                                T * S / G, (int)(T * S % G), ws.slots, ws.flags,
+                                                ws.timeout, ws.seq, rarg);
           DM_CHECK(hipGetLastError());
           return;
         }
@@ -716,25 +701,15 @@ void launch_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD
   set_smem_attr(k, sm);
   if (ntN > 1) {
     const unsigned mt8 = (unsigned)((mtiles + 7) / 8 * 8);
-    k<<<dim3(mt8 * ntN, ng), NT, sm, st>>>(X, Wp, Y, ADD, stats, gs, xb, wb, ntN, mtiles, 1, rarg,
-                                            sarg);
+    k<<<dim3(mt8 * ntN, ng), NT, sm, st>>>(o.X, o.Wp, o.Y, o.add, o.stats, gs, xb, wb, ntN, mtiles,
+                                            1, rarg, sarg);
   } else {
-    k<<<dim3((unsigned)mtiles, ng), NT, sm, st>>>(X, Wp, Y, ADD, stats, gs, xb, wb, 1, mtiles, 0,
-                                                  rarg, sarg);
+    k<<<dim3((unsigned)mtiles, ng), NT, sm, st>>>(o.X, o.Wp, o.Y, o.add, o.stats, gs, xb, wb, 1,
+                                                  mtiles, 0, rarg, sarg);
   }
   DM_CHECK(hipGetLastError());
 }
 
-// launch_pipe on the tile of a pipe row of conv_cfg.h; false for any other cfg
-bool launch_pipe_cfg(int cfg, const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
-                     float* stats, const ConvGeomSet& gs, int ng, hipStream_t st,
-                     const BnBwdRed* red, const DgradSeg2* seg2, int sched) {
-  return with_cfg_row<kConvCfgs, ConvFamily::pipe>(cfg, [&](auto row) {
-    constexpr ConvCfg c = kConvCfgs[decltype(row)::value];
-    static_assert(c.bm == PBM, "the pipe kernels' row tile");
-    launch_pipe<c.bn, c.wm, c.wn, c.minw>(X, Wp, Y, ADD, stats, gs, ng, st, red, seg2, sched);
-  });
-}
 }  // namespace
 
 void conv_pipe_set_workspace(PipeWorkspaceFn fn) { g_pipe_ws = fn; }
@@ -749,21 +724,16 @@ bool conv_pipe_supported(const ConvGeom& g, int cfg) {
   return true;
 }
 
-void conv_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-               const ConvGeom& g, int cfg, hipStream_t st, const BnBwdRed* red, int sched) {
-  if (!launch_pipe_cfg(cfg, X, Wp, Y, ADD, stats, ConvGeomSet::one(g), 1, st, red, nullptr, sched))
-    throw std::runtime_error("conv_pipe: not a pipelined cfg");
-}
-
-// the parity classes of a stride-2 data gradient (no statistics) in one launch
-bool conv_pipe_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
-                     const ConvGeomSet& gs, int ng, int cfg, hipStream_t st, const DgradSeg2* seg2,
-                     const BnBwdRed* red, int sched) {
-  if (ng < 1 || ng > 4) return false;
-  for (int i = 0; i < ng; ++i)
-    if (!conv_pipe_supported(gs.g[i], cfg)) return false;
-  if (seg2 && seg2->C2 != gs.g[0].C) return false;
-  return launch_pipe_cfg(cfg, X, Wp, Y, ADD, nullptr, gs, ng, st, red, seg2, sched);
+// one launch of the row's tile over ng geometries sharing X / W / Y
+void conv_pipe(const ConvOperands& o, const ConvGeomSet& gs, int ng, const ConvCfg& cfg,
+               hipStream_t st) {
+  const auto launch = [&](auto row) {
+    constexpr ConvCfg c = kConvCfgs[decltype(row)::value];
+    static_assert(c.bm == PBM, "the pipe kernels' row tile");
+    launch_pipe<c.bn, c.wm, c.wn, c.minw>(o, gs, ng, st);
+  };
+  if (ng < 1 || ng > 4 || !with_cfg_row<kConvCfgs, ConvFamily::pipe>(cfg.id, launch))
+    throw std::runtime_error("conv_pipe: a pipelined cfg and 1 to 4 geometries");
 }
 
 }  // namespace dm

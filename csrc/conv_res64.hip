@@ -30,7 +30,6 @@
 // Workgroups own contiguous tile ranges, so the 2W+2 halo rows two consecutive tiles share
 // are re-read from this XCD's L2, not HBM.
 #include "common.h"
-#include "conv_geom.h"
 #include "igemm_common.h"
 #include "kernels.h"
 
@@ -417,20 +416,11 @@ __global__ void __launch_bounds__(RNT, 2) conv_res64_kernel(
   }
 }
 
-int cu_count() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    DM_CHECK(hipGetDevice(&dev));
-    DM_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  }
-  return cus;
-}
 }  // namespace
 
 int res64_grid(long long M) {
   const long long ntiles = (M + RT - 1) / RT;
-  const long long g = 2LL * cu_count();  // two workgroups per CU
+  const long long g = 2LL * device_cu_count();  // two workgroups per CU
   return (int)(ntiles < g ? ntiles : g);
 }
 
@@ -449,26 +439,24 @@ bool conv_res64_supported(const ConvGeom& g) {
   return true;
 }
 
-void conv_res64(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-                const ConvGeom& g, hipStream_t st, const float* pre_sc, const float* pre_sh,
-                const BnBwdRed* red) {
+void conv_res64(const ConvOperands& o, const ConvGeom& g, const ConvCfg&, hipStream_t st) {
   if (!conv_res64_supported(g)) throw std::runtime_error("conv_res64: unsupported geometry");
   const int grid = res64_grid(g.M);
   const unsigned bytes = (unsigned)(g.M * RC * 2);
   const int ntiles = (int)((g.M + RT - 1) / RT);
-  if (red) {
-    if (pre_sc || !red->y || !red->sc || !red->sh || !red->mu || !red->is ||
-        !red->part)
+  if (o.red) {
+    if (o.pre_sc || !o.red->y || !o.red->sc || !o.red->sh || !o.red->mu || !o.red->is ||
+        !o.red->part)
       throw std::runtime_error("conv_res64: BN-backward reduction needs y, sc, sh, mu, is, part "
                                "(no PRE input)");
     set_smem_attr(conv_res64_kernel<false, true>, R_SMEM_RED);
     conv_res64_kernel<false, true><<<grid, RNT, R_SMEM_RED, st>>>(
-        X, Wp, Y, ADD, stats, g, bytes, bytes, pre_sc, pre_sh, ntiles, *red);
+        o.X, o.Wp, o.Y, o.add, o.stats, g, bytes, bytes, o.pre_sc, o.pre_sh, ntiles, *o.red);
   } else {
-    auto k = pre_sc ? conv_res64_kernel<true, false> : conv_res64_kernel<false, false>;
+    auto k = o.pre_sc ? conv_res64_kernel<true, false> : conv_res64_kernel<false, false>;
     set_smem_attr(k, R_SMEM);
-    k<<<grid, RNT, R_SMEM, st>>>(X, Wp, Y, ADD, stats, g, bytes, bytes, pre_sc, pre_sh, ntiles,
-                                 BnBwdRed{});
+    k<<<grid, RNT, R_SMEM, st>>>(o.X, o.Wp, o.Y, o.add, o.stats, g, bytes, bytes, o.pre_sc,
+                                 o.pre_sh, ntiles, BnBwdRed{});
   }
   DM_CHECK(hipGetLastError());
 }

@@ -20,7 +20,6 @@
 // 16-lane group.  A halo pixel is 32 B (two 16-B halves); its halves are swapped when
 // (pixel >> 3) & 1, so 16 consecutive pixels reading the same half cover all 16 slots.
 #include "common.h"
-#include "conv_geom.h"
 #include "igemm_common.h"
 #include "kernels.h"
 
@@ -573,21 +572,15 @@ void stem_wgrad_fused(const bf16_t* xs, const bf16_t* y, const bf16_t* pdy, cons
   DM_CHECK(hipGetLastError());
 }
 
-void stem_conv(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, float* stats, const ConvGeom& g,
-               hipStream_t st) {
+void stem_conv(const ConvOperands& o, const ConvGeom& g, const ConvCfg&, hipStream_t st) {
   const unsigned xb = (unsigned)((long long)g.N * g.H * g.W * g.C * 2);
   const int ntiles = (int)((g.M + SBM - 1) / SBM);
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    DM_CHECK(hipGetDevice(&dev));
-    DM_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  }
+  const int cus = device_cu_count();
   const size_t hal = (size_t)(SHP + 1) * SC * 2, band = (size_t)128 * (SCO + 4) * 4;
   const size_t smp = (size_t)SCO * SK * 2 + (hal > band ? hal : band) + MAXTAPS * 16;
   set_smem_attr(stem_conv_pers_kernel, smp);
   const int grid = ntiles < 2 * cus ? ntiles : 2 * cus;
-  stem_conv_pers_kernel<<<grid, 256, smp, st>>>(X, Wp, Y, stats, g, xb, ntiles);
+  stem_conv_pers_kernel<<<grid, 256, smp, st>>>(o.X, o.Wp, o.Y, o.stats, g, xb, ntiles);
   DM_CHECK(hipGetLastError());
 }
 

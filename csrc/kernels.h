@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "conv_cfg.h"
+#include "conv_geom.h"
+
 namespace dm {
 typedef unsigned short bf16_t;
 
@@ -132,24 +135,64 @@ void p2p_xgmi_send(const void* src, long long bytes, void* ring, void* full, con
                    long long slot_bytes, int nslot, unsigned* state, hipStream_t st);
 void p2p_xgmi_recv(void* dst, long long bytes, const void* ring, const void* full, void* free_,
                    long long slot_bytes, int nslot, unsigned* state, hipStream_t st);
-// conv_igemm.hip; every `cfg` below is an id of csrc/conv_cfg.h
-struct ConvGeom;
-struct ConvGeomSet;
-struct DgradSeg2;
+// ---- the conv launches; every `cfg` below is an id / a row of csrc/conv_cfg.h
 struct BnBwdRed;
-// seg2 (optional): a second K segment of geometry seg2->z (a 1x1/s2 projection's data
-// gradient merged into the stride-2 dgrad's parity class (0,0)); red (optional): the consumer
-// BatchNorm's backward sums in the epilogue (one part row per block, class-major)
-bool igemm_fwd_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-                     const ConvGeomSet& gs, int ng, int cfg, hipStream_t st,
-                     const DgradSeg2* seg2 = nullptr, const BnBwdRed* red = nullptr);
-// pipe_sched: the pipelined tiles' schedule (conv_pipe's sched); the other kernels have none
-void igemm_fwd(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-               const ConvGeom& g, int cfg, hipStream_t st, int pipe_sched = -1);
+// sched: the pipelined tiles' schedule (the other kernels have none).  kPipeAuto = the launcher
+// decides (conv_pipe_plan.h), 0 = the data-parallel launch, G > 0 = the balanced schedule on G
+// workgroups wherever it is eligible (tests and A/B runs)
+constexpr int kPipeAuto = -1;
+// The operands of a forward-style conv GEMM (forward, stride-1 dgrad, the parity classes of a
+// stride-2 dgrad); everything after Y is optional.  add: added to the result; stats [T][2][Cout]:
+// the BatchNorm batch statistics; pre_sc / pre_sh: X is staged as relu(X*pre_sc + pre_sh); red:
+// the consumer BatchNorm's backward sums in the epilogue (one part row per block, class-major);
+// seg2: a second K segment of geometry seg2->z (a 1x1/s2 projection's data gradient merged into
+// the stride-2 dgrad's parity class (0,0))
+struct ConvOperands {
+  const bf16_t *X, *Wp;
+  bf16_t* Y;
+  int sched;
+  const bf16_t* add;
+  float* stats;
+  const float *pre_sc, *pre_sh;
+  const BnBwdRed* red;
+  const DgradSeg2* seg2;
+};
+// The operands of a weight gradient into S fp32 slabs [Cout][K] (rows split in chunks of mchunk)
+struct WgradOperands {
+  const bf16_t *X, *DY;
+  float* slab;
+  int S;
+  long long mchunk;
+  const float *pre_sc, *pre_sh;
+};
+// conv_launch.cpp: the dispatcher.  The one place that evaluates the *_supported predicates,
+// asks conv_cfg.h's route functions and names a family's launcher; a refused route throws
+// std::runtime_error.  conv_launch_multi: up to four geometries sharing X / W / Y (the parity
+// classes of a stride-2 dgrad) in one launch, or one launch per class (data-parallel schedule)
+// where the row has none; false = refused (a merged segment / RED needs the single launch).
+// dry: the route (conv_cfg.h) is reported there and nothing is launched
+void conv_launch(const ConvOperands& ops, const ConvGeom& g, const ConvCfg& cfg, hipStream_t st,
+                 ConvRoute* dry = nullptr);
+bool conv_launch_multi(const ConvOperands& ops, const ConvGeomSet& gs, int ng, const ConvCfg& cfg,
+                       hipStream_t st, ConvRoute* dry = nullptr);
+void wgrad_launch(const WgradOperands& ops, const ConvGeom& g, const WgradCfg& cfg, hipStream_t st,
+                  WgradRoute* dry = nullptr);
+// statistics / part rows a single-geometry launch of this row writes (one per row tile, or per
+// workgroup of the persistent res64 kernel), and the part rows of the classes' single launch with
+// RED (class major, row tile minor; every block writes its row); 0 if the row has no such launch
+long long conv_stats_rows(long long M, const ConvCfg& cfg);
+long long conv_multi_red_rows(const ConvGeomSet& gs, int ng, const ConvCfg& cfg);
+// compute units of the current device (cached per device): the grid limit of the persistent
+// kernels (res64, stem, the pipelined tiles' balanced schedule); defined next to the dispatcher
+int device_cu_count();
+// conv_igemm.hip: the igemm tiles (cfg: an igemm row; ng geometries, blockIdx.z = geometry) and
+// the v2 weight-gradient tiles
+void igemm_tile(const ConvOperands& ops, const ConvGeomSet& gs, int ng, const ConvCfg& cfg,
+                hipStream_t st);
+void wgrad_tile(const WgradOperands& ops, const ConvGeom& g, const WgradCfg& cfg, hipStream_t st);
 // conv_stem.hip: s2d stem (16 channels, 16 taps, 64 outputs) with resident weights (cfg 60)
 bool stem_conv_supported(const ConvGeom& g);
-void stem_conv(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, float* stats, const ConvGeom& g,
-               hipStream_t st);
+void stem_conv(const ConvOperands& ops, const ConvGeom& g, const ConvCfg& cfg, hipStream_t st);
 // fused stem BN backward (quad max-pool gather) + s2d weight gradient -> slabs [S][64][256]
 bool stem_wgrad_fused_supported(int N, int H, int W, int C, int Cpad);
 int stem_wgrad_fused_blocks(int N, int H);
@@ -184,24 +227,14 @@ void stem_pack_weights(const float* w, bf16_t* wk, hipStream_t st);
 struct BnBwdRed {
   const bf16_t* y;
   const uint8_t* mask;
-  const float* sc;
-  const float* sh;
-  const float* mu;
-  const float* is;
+  const float *sc, *sh, *mu, *is;
   float* part;
 };
-// conv_pipe.hip: pipelined LDS-DMA implicit-GEMM conv (cfg 90-93: 256-pixel tiles)
+// conv_pipe.hip: pipelined LDS-DMA implicit-GEMM conv (cfg 90-93: 256-pixel tiles); ng
+// geometries (blockIdx.y = geometry), no statistics with more than one
 bool conv_pipe_supported(const ConvGeom& g, int cfg);
-bool conv_pipe_multi(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD,
-                     const ConvGeomSet& gs, int ng, int cfg, hipStream_t st,
-                     const DgradSeg2* seg2 = nullptr, const BnBwdRed* red = nullptr,
-                     int sched = -1);
-// sched: kPipeAuto = the launcher decides (conv_pipe_plan.h), 0 = the data-parallel launch,
-// G > 0 = the balanced schedule on G workgroups wherever it is eligible (tests and A/B runs)
-constexpr int kPipeAuto = -1;
-void conv_pipe(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-               const ConvGeom& g, int cfg, hipStream_t st, const BnBwdRed* red = nullptr,
-               int sched = kPipeAuto);
+void conv_pipe(const ConvOperands& ops, const ConvGeomSet& gs, int ng, const ConvCfg& cfg,
+               hipStream_t st);
 // The balanced schedule's workspace of one (device, stream), owned by the bindings: `cap` slots
 // of 256 x 256 fp32 accumulators, `cap` flag words and the timeout word, all zero at first; seq
 // is this launch's sequence number (a host counter per workspace, never 0), so that no word is
@@ -219,31 +252,21 @@ void conv_pipe_set_workspace(PipeWorkspaceFn fn);
 // statistics rows = res64_grid(M) (one per workgroup)
 bool conv_res64_supported(const ConvGeom& g);
 int res64_grid(long long M);
-void conv_res64(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-                const ConvGeom& g, hipStream_t st, const float* pre_sc = nullptr,
-                const float* pre_sh = nullptr, const BnBwdRed* red = nullptr);
-// conv_halo.hip: halo-staged unit-stride tiles; bn / waves = the row's bn / halo_waves (conv_cfg.h)
+void conv_res64(const ConvOperands& ops, const ConvGeom& g, const ConvCfg& cfg, hipStream_t st);
+// conv_halo.hip: halo-staged unit-stride tiles (the row's bn / halo_waves select the tile)
 bool conv_halo_supported(const ConvGeom& g);
-void conv_halo(const bf16_t* X, const bf16_t* Wp, bf16_t* Y, const bf16_t* ADD, float* stats,
-               const ConvGeom& g, int bn, int waves, hipStream_t st,
-               const float* pre_sc = nullptr, const float* pre_sh = nullptr,
-               const BnBwdRed* red = nullptr);
+void conv_halo(const ConvOperands& ops, const ConvGeom& g, const ConvCfg& cfg, hipStream_t st);
+// wgrad_halo.hip: halo-staged 3x3 unit-stride weight gradient (wgrad cfg 4, 5: taps per block)
 bool wgrad_halo_supported(const ConvGeom& g);
+void wgrad_halo(const WgradOperands& ops, const ConvGeom& g, const WgradCfg& cfg, hipStream_t st);
 // stride-2 3x3 weight gradient over the four input parity planes (wgrad cfg 7)
 bool wgrad_s2_supported(const ConvGeom& g);
-void wgrad_s2(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
-              long long mchunk, hipStream_t st);
+void wgrad_s2(const WgradOperands& ops, const ConvGeom& g, const WgradCfg& cfg, hipStream_t st);
 // wgrad_res64.hip: row-streaming 64 -> 64 channel 3x3 weight gradient (wgrad cfg 8); S slabs
 bool wgrad_res64_supported(const ConvGeom& g);
-void wgrad_res64(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
-                 hipStream_t st, const float* pre_sc = nullptr, const float* pre_sh = nullptr);
-void wgrad_halo(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
-                long long mchunk, int nty, hipStream_t st, const float* pre_sc = nullptr,
-                const float* pre_sh = nullptr);
+void wgrad_res64(const WgradOperands& ops, const ConvGeom& g, const WgradCfg& cfg, hipStream_t st);
 void pack_weights_tiled(const long long* desc, const int* tprefix, int nl, int ntiles,
                         hipStream_t st);
-void igemm_wgrad(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
-                 long long mchunk, int cfg, hipStream_t st);
 void wgrad_reduce(const float* slab, int S, int Cout, int C, int Cin, int KH, int KW, float* dw,
                   float beta, hipStream_t st);
 void pack_weights(const float* w, bf16_t* wf, bf16_t* wd, int Cout, int Cin, int Cpad, int KH,

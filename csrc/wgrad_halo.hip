@@ -24,7 +24,6 @@
 // fragments.  The m reduction is split over blocks into fp32 slabs [S][Cout][9*C] reduced
 // by wgrad_reduce (fixed order, deterministic).
 #include "common.h"
-#include "conv_geom.h"
 #include "igemm_common.h"
 #include "kernels.h"
 
@@ -367,44 +366,42 @@ __global__ void __launch_bounds__(256, MR == 32 ? 2 : 1) wgrad_s2_kernel(
 }
 
 template <int HRN, int MR>
-void launch_wgrad_s2(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
-                     long long mchunk, hipStream_t st) {
+void launch_wgrad_s2(const WgradOperands& o, const ConvGeom& g, hipStream_t st) {
   const size_t sm = ((size_t)2 * MR * WPITCH + (size_t)2 * HRN * 32 * WPITCH + WPITCH) * 2;
-  dim3 grid((g.Ncols + WBM - 1) / WBM, g.C / WBC, S);
+  dim3 grid((g.Ncols + WBM - 1) / WBM, g.C / WBC, o.S);
   const unsigned xb = (unsigned)((long long)g.N * g.H * g.W * g.C * 2);
   const unsigned db = (unsigned)(g.M * g.Ncols * 2);
   auto k = wgrad_s2_kernel<HRN, MR>;
   set_smem_attr(k, sm);
   const int xy = (int)(grid.x * grid.y);
-  if (xy > 1 && S > 1) {
-    const unsigned z8 = (unsigned)((S + 7) / 8 * 8);
-    k<<<dim3(z8 * xy), 256, sm, st>>>(X, DY, slab, g, mchunk, xb, db, xy, (int)grid.x, S);
+  if (xy > 1 && o.S > 1) {
+    const unsigned z8 = (unsigned)((o.S + 7) / 8 * 8);
+    k<<<dim3(z8 * xy), 256, sm, st>>>(o.X, o.DY, o.slab, g, o.mchunk, xb, db, xy, (int)grid.x, o.S);
     return;
   }
-  k<<<grid, 256, sm, st>>>(X, DY, slab, g, mchunk, xb, db, 0, (int)grid.x, S);
+  k<<<grid, 256, sm, st>>>(o.X, o.DY, o.slab, g, o.mchunk, xb, db, 0, (int)grid.x, o.S);
 }
 
 template <int HRN, int NTY>
-void launch_wgrad_halo(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
-                       long long mchunk, hipStream_t st, const float* pre_sc,
-                       const float* pre_sh) {
+void launch_wgrad_halo(const WgradOperands& o, const ConvGeom& g, hipStream_t st) {
   const size_t sm = ((size_t)2 * WBK * WPITCH + (size_t)2 * HRN * 32 * WPITCH + WPITCH) * 2;
-  dim3 grid((g.Ncols + WBM - 1) / WBM, (g.C / WBC) * (3 / NTY), S);
+  dim3 grid((g.Ncols + WBM - 1) / WBM, (g.C / WBC) * (3 / NTY), o.S);
   const unsigned xb = (unsigned)((long long)g.N * g.H * g.W * g.C * 2);
   const unsigned db = (unsigned)(g.M * g.Ncols * 2);
-  auto k = pre_sc ? wgrad_halo_kernel<HRN, NTY, true> : wgrad_halo_kernel<HRN, NTY, false>;
+  auto k = o.pre_sc ? wgrad_halo_kernel<HRN, NTY, true> : wgrad_halo_kernel<HRN, NTY, false>;
   set_smem_attr(k, sm);
   // XCD-grouped order for the 9-tap tiles.  Measured (tools/bench_conv.py, one call): 9-tap
   // layer2 +2-4 %, layer3/4 within 1 %, step 11.55 vs 11.57 ms; the 3-tap tiles lose (layer1
   // 526 -> 475 TF/s) and keep the 3-D grid
   const int xy = (int)(grid.x * grid.y);
-  if (NTY == 3 && xy > 1 && S > 1) {
-    const unsigned z8 = (unsigned)((S + 7) / 8 * 8);
-    k<<<dim3(z8 * xy), 256, sm, st>>>(X, DY, slab, g, mchunk, xb, db, pre_sc, pre_sh, xy,
-                                       (int)grid.x, S);
+  if (NTY == 3 && xy > 1 && o.S > 1) {
+    const unsigned z8 = (unsigned)((o.S + 7) / 8 * 8);
+    k<<<dim3(z8 * xy), 256, sm, st>>>(o.X, o.DY, o.slab, g, o.mchunk, xb, db, o.pre_sc, o.pre_sh,
+                                       xy, (int)grid.x, o.S);
     return;
   }
-  k<<<grid, 256, sm, st>>>(X, DY, slab, g, mchunk, xb, db, pre_sc, pre_sh, 0, (int)grid.x, S);
+  k<<<grid, 256, sm, st>>>(o.X, o.DY, o.slab, g, o.mchunk, xb, db, o.pre_sc, o.pre_sh, 0,
+                           (int)grid.x, o.S);
 }
 }  // namespace
 
@@ -430,27 +427,25 @@ bool wgrad_s2_supported(const ConvGeom& g) {
   return 4 * 32 + 2 * g.Wg + 2 <= 6 * 32;
 }
 
-void wgrad_s2(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
-              long long mchunk, hipStream_t st) {
+void wgrad_s2(const WgradOperands& o, const ConvGeom& g, const WgradCfg&, hipStream_t st) {
   if (!wgrad_s2_supported(g)) throw std::runtime_error("wgrad_s2: unsupported geometry");
   // 32-row steps: 72 KB of LDS, two workgroups per CU (64-row steps, one per CU, lost 0.7 %:
   // profiles/wgrad_s2_ab_r4al.txt, profiles/wgrad_s2_mr_ab_r4am.txt)
   const int rows = 4 * 32 + 2 * g.Wg + 2;
-  if (rows <= 5 * 32) launch_wgrad_s2<5, 32>(X, DY, slab, g, S, mchunk, st);
-  else launch_wgrad_s2<6, 32>(X, DY, slab, g, S, mchunk, st);
+  if (rows <= 5 * 32) launch_wgrad_s2<5, 32>(o, g, st);
+  else launch_wgrad_s2<6, 32>(o, g, st);
   DM_CHECK(hipGetLastError());
 }
 
-void wgrad_halo(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
-                long long mchunk, int nty, hipStream_t st, const float* pre_sc,
-                const float* pre_sh) {
-  if (nty == 1) {
-    launch_wgrad_halo<3, 1>(X, DY, slab, g, S, mchunk, st, pre_sc, pre_sh);  // 66 rows
+// the row's taps per block: 3 (one kernel row, NTY = 1) or 9 (NTY = 3)
+void wgrad_halo(const WgradOperands& o, const ConvGeom& g, const WgradCfg& cfg, hipStream_t st) {
+  if (cfg.taps / 3 == 1) {
+    launch_wgrad_halo<3, 1>(o, g, st);  // 66 rows
   } else {
     const int rows = WBK + 2 * g.W + 2;
-    if (rows <= 96) launch_wgrad_halo<3, 3>(X, DY, slab, g, S, mchunk, st, pre_sc, pre_sh);
-    else if (rows <= 128) launch_wgrad_halo<4, 3>(X, DY, slab, g, S, mchunk, st, pre_sc, pre_sh);
-    else launch_wgrad_halo<6, 3>(X, DY, slab, g, S, mchunk, st, pre_sc, pre_sh);
+    if (rows <= 96) launch_wgrad_halo<3, 3>(o, g, st);
+    else if (rows <= 128) launch_wgrad_halo<4, 3>(o, g, st);
+    else launch_wgrad_halo<6, 3>(o, g, st);
   }
   DM_CHECK(hipGetLastError());
 }

@@ -29,7 +29,6 @@
 //    landed input pieces before the barrier that publishes them;
 //  * each workgroup writes one fp32 slab [64][576], reduced in fixed order by wgrad_reduce.
 #include "common.h"
-#include "conv_geom.h"
 #include "igemm_common.h"
 #include "kernels.h"
 
@@ -285,15 +284,14 @@ bool wgrad_res64_supported(const ConvGeom& g) {
 }
 
 // S = slab count = workgroups (each owns a contiguous range of the N*H image rows)
-void wgrad_res64(const bf16_t* X, const bf16_t* DY, float* slab, const ConvGeom& g, int S,
-                 hipStream_t st, const float* pre_sc, const float* pre_sh) {
+void wgrad_res64(const WgradOperands& o, const ConvGeom& g, const WgradCfg&, hipStream_t st) {
   if (!wgrad_res64_supported(g)) throw std::runtime_error("wgrad_res64: unsupported geometry");
   const int nrows = g.N * g.H;
-  if (S < 1 || S > nrows) throw std::runtime_error("wgrad_res64: S must be in [1, N*H]");
+  if (o.S < 1 || o.S > nrows) throw std::runtime_error("wgrad_res64: S must be in [1, N*H]");
   const unsigned bytes = (unsigned)((long long)g.N * g.H * g.W * QC * 2);
-  auto k = pre_sc ? wgrad_res64_kernel<true> : wgrad_res64_kernel<false>;
+  auto k = o.pre_sc ? wgrad_res64_kernel<true> : wgrad_res64_kernel<false>;
   set_smem_attr(k, Q_SMEM);
-  k<<<S, 512, Q_SMEM, st>>>(X, DY, slab, g, bytes, bytes, pre_sc, pre_sh, nrows);
+  k<<<o.S, 512, Q_SMEM, st>>>(o.X, o.DY, o.slab, g, bytes, bytes, o.pre_sc, o.pre_sh, nrows);
   DM_CHECK(hipGetLastError());
 }
 

@@ -7,7 +7,10 @@ reference of tests/exact_conv.py bit for bit, element by element, in any accumul
 Outputs are NaN-prefilled views between guard regions (a missed element or a write past the
 tensor shows); inputs sit between NaN guards (a read past an operand that reaches a MAC
 poisons the result).  Where a cfg does not take a shape and the dispatcher falls back the
-result must still be exact; where the binding refuses the shape it must raise."""
+result must still be exact; where the binding refuses the shape it must raise.  Which kernel
+runs is asserted too (conv_route_info / wgrad_route_info against the limits restated below):
+the specialised family where the shape fits, the documented fallback tile where it does not,
+so a silent fallback fails."""
 import functools
 
 import pytest
@@ -59,6 +62,59 @@ def _wgrad_halo_ok(geom):
 def _wgrad_res64_ok(geom):
     N, H, W, Cin, Cout, k, s, p = geom
     return (Cin, Cout, k, s, p) == (64, 64, 3, 1, 1) and W <= 60
+
+
+def _wgrad_s2_ok(geom):
+    """Stride-2 3x3/p1 over the parity planes of an even image, output rows up to 31 wide."""
+    N, H, W, Cin, Cout, k, s, p = geom
+    return (k, s, p) == (3, 2, 1) and H % 2 == 0 and W % 2 == 0 and Cin % 64 == 0 and W // 2 <= 31
+
+
+# ---- the kernel each launch must run on: (family, tile), or None where it must be refused
+REFUSED = None
+IGEMM_FALLBACK = {39: -1, 41: -1, 42: 12}  # halo cfg -> igemm tile (csrc/conv_cfg.h fallback)
+
+
+def _conv_route(geom, cfg, dgrad=False, pre=False, red=False):
+    """One geometry (forward, or the stride-1 data gradient, whose GEMM reads Cout channels and
+    writes Cin columns).  No fallback tile takes a pre-BN operand or the reduction epilogue."""
+    N, H, W, Cin, Cout, k, s, p = geom
+    cin, ncols = (Cout, Cin) if dgrad else (Cin, Cout)
+    special = pre or red
+    if cfg == 80:
+        return ("res64", 80) if _res64_ok(geom) else REFUSED
+    if cfg in HALO_CFGS or (pre and cfg in PIPE_BN):  # a pre-BN launch on 90-93 runs on 41
+        row = 41 if cfg in PIPE_BN else cfg
+        if red and row != 42:
+            return REFUSED
+        if _halo_ok(W, cin, k, s, p):
+            return ("halo", row)
+        return REFUSED if special else ("igemm", IGEMM_FALLBACK[cfg])
+    if cfg in PIPE_BN:
+        if _pipe_ok(cfg, cin, ncols):
+            return ("pipe", cfg)
+        return REFUSED if special else ("igemm", -2 if ncols % 128 == 0 else -1)
+    return REFUSED if special else ("igemm", cfg)
+
+
+def _wgrad_route(geom, cfg, pre=False):
+    Cout = geom[4]
+    if cfg == 8:
+        return ("res64", 8) if _wgrad_res64_ok(geom) else REFUSED
+    fits = {4: _wgrad_halo_ok, 5: _wgrad_halo_ok, 7: _wgrad_s2_ok}.get(cfg)
+    if fits is None:
+        return REFUSED if pre else ("v2", cfg)
+    if fits(geom) and not (pre and cfg == 7):
+        return ("s2" if cfg == 7 else "halo", cfg)
+    return REFUSED if pre else ("v2", 2 if Cout % 128 == 0 else 3)
+
+
+def _assert_route(got, want, what):
+    family, tile, ok = got
+    if want is REFUSED:
+        assert not ok, f"{what}: must be refused, routed to {family} {tile}"
+    else:
+        assert ok and (family, tile) == want, f"{what}: runs on {got}, expected {want}"
 
 
 # ---- device operands of one case, each between NaN (0xFF) guards, shared by the tests
@@ -121,6 +177,10 @@ def _stats_sum(buf, rows, C):
 # ------------------------------------------------------------------ forward
 def _fwd(d, cfg, add, pre, supported):
     N, H, W, Cin, Cout, k, s, p = d.geom
+    want = _conv_route(d.geom, cfg, pre=pre)
+    assert supported == (want is not REFUSED)
+    _assert_route(lib().conv_route_info(N, H, W, Cin, Cout, k, s, p, cfg, add=add, pre=pre), want,
+                  f"fwd cfg {cfg} add={add} pre={pre}")
     OH, OW = ec.out_hw(d.geom)
     M = N * OH * OW
     y, ychk = d.out((N, OH, OW, Cout))
@@ -165,9 +225,13 @@ def test_fwd_prebn_exact(dev, geom, cfg, add):
 
 
 # ------------------------------------------------------------------ data gradient
-def _dgrad(d, cfg, mode, supported=True, red=None):
+UNCHECKED = object()  # a refusal that is the binding's operand check, not a route
+
+
+def _dgrad(d, cfg, mode, supported=True, red=None, route=UNCHECKED):
     """mode: plain | acc (in place) | masked (add + 1-bit add_mask) | merged (dy2 / wd2).
-    red: None, "y" (mask from red_y*scale + shift > 0) or "bits" (1-bit red_mask)."""
+    red: None, "y" (mask from red_y*scale + shift > 0) or "bits" (1-bit red_mask).
+    route: the (family, tile) the launch must run on, REFUSED, or UNCHECKED."""
     N, H, W, Cin, Cout, k, s, p = d.geom
     dx, xchk = d.out((N, H, W, Cin))
     add, kw = None, {}
@@ -188,6 +252,11 @@ def _dgrad(d, cfg, mode, supported=True, red=None):
                   red_invstd=d.red_invstd, red_part=part)
         if red == "bits":
             kw["red_mask"] = d.red_keep
+    if route is not UNCHECKED:
+        assert supported == (route is not REFUSED)
+        _assert_route(lib().conv_route_info(N, H, W, Cin, Cout, k, s, p, cfg, add=add is not None,
+                                            red=bool(red), dgrad=True, merged=mode == "merged"),
+                      route, f"dgrad cfg {cfg} {mode} red={red}")
     call = lambda: lib().conv_dgrad(d.dy, d.wd, dx, k, k, s, p, add, cfg, **kw)
     if not supported:
         with pytest.raises(RuntimeError):
@@ -210,14 +279,16 @@ def _dgrad(d, cfg, mode, supported=True, red=None):
 @pytest.mark.parametrize("mode", ["plain", "acc"])
 def test_dgrad_s1_exact(dev, geom, cfg, mode):
     _skip_wide(cfg, geom[3])
-    _dgrad(_case(dev, geom), cfg, mode, cfg != 80 or _res64_ok(geom))
+    _dgrad(_case(dev, geom), cfg, mode, cfg != 80 or _res64_ok(geom),
+           route=_conv_route(geom, cfg, dgrad=True))
 
 
 @geoms("geom", ec.GEOMS_S1)
 @pytest.mark.parametrize("cfg", [80, 42, 39, 90, 13])
 def test_dgrad_s1_masked_add_exact(dev, geom, cfg):
     """Fused identity skip: dx = dgrad(dy) + add where the 1-bit mask is set."""
-    _dgrad(_case(dev, geom), cfg, "masked", cfg != 80 or _res64_ok(geom))
+    _dgrad(_case(dev, geom), cfg, "masked", cfg != 80 or _res64_ok(geom),
+           route=_conv_route(geom, cfg, dgrad=True))
 
 
 @geoms("geom", ec.GEOMS_STRIDE2)
@@ -228,13 +299,17 @@ def test_dgrad_s2_exact(dev, geom, cfg, mode):
     zero-filled), in place, and with the 1x1/s2 projection merged into class (0,0)."""
     N, H, W, Cin, Cout, k, s, p = geom
     _skip_wide(cfg, Cin)
-    ok = True
+    # the classes' one launch: the igemm tiles always; a pipelined tile where it fits, else one
+    # launch per class (tile 0), which takes no merged segment
+    ok, route = True, ("igemm", cfg)
+    if cfg in PIPE_BN:
+        route = ("pipe", cfg if _pipe_ok(cfg, Cout, Cin) else 0)
     if mode == "merged":
         if not ec.has_projection(geom):
-            ok = False  # only a 3x3/s2/p1 data gradient merges: refused
-        elif cfg in PIPE_BN:
-            ok = _pipe_ok(cfg, Cout, Cin)  # a pipelined tile that does not fit is refused
-    _dgrad(_case(dev, geom), cfg, mode, ok)
+            ok, route = False, UNCHECKED  # only a 3x3/s2/p1 data gradient merges: refused
+        elif route == ("pipe", 0):
+            ok, route = False, REFUSED  # a pipelined tile that does not fit is refused
+    _dgrad(_case(dev, geom), cfg, mode, ok, route=route)
 
 
 @geoms("geom", ec.GEOMS_S1)
@@ -246,7 +321,8 @@ def test_dgrad_s1_bn_reduce_exact(dev, geom, cfg, masked):
     N, H, W, Cin, Cout, k, s, p = geom
     ok = (_res64_ok(geom) if cfg == 80 else _halo_ok(W, Cout, k, s, p) if cfg == 42
           else _pipe_ok(cfg, Cout, Cin))
-    _dgrad(_case(dev, geom), cfg, "masked" if masked else "plain", ok, "bits" if masked else "y")
+    _dgrad(_case(dev, geom), cfg, "masked" if masked else "plain", ok, "bits" if masked else "y",
+           route=_conv_route(geom, cfg, dgrad=True, red=True))
 
 
 @geoms("geom", ec.GEOMS_STRIDE2)
@@ -262,6 +338,12 @@ def test_dgrad_s2_bn_reduce_exact(dev, geom, cfg, src, mode):
 # ------------------------------------------------------------------ weight gradient
 def _wgrad(d, cfg, S, beta, pre, supported=True):
     N, H, W, Cin, Cout, k, s, p = d.geom
+    want = _wgrad_route(d.geom, cfg, pre)
+    # (cfg 8 also refuses a slab count past the image rows: the route exists, the launcher's
+    # own guard raises)
+    assert supported == (want is not REFUSED) or (cfg == 8 and not supported)
+    _assert_route(lib().wgrad_route_info(N, H, W, Cin, Cout, k, s, p, cfg, pre=pre), want,
+                  f"wgrad cfg {cfg} pre={pre}")
     K = k * k * _cpad(Cin)
     dw, wchk = d.out((Cout, Cin, k, k), F32)
     slab, schk = d.out((S * Cout * K,), F32)

@@ -35,6 +35,19 @@ def test_cfg_table_asan_ubsan(tmp_path):
     assert r.stdout.splitlines()[-1] == "ok", r.stdout
 
 
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
+def test_conv_route_asan_ubsan(tmp_path):
+    """The conv routing rule (csrc/conv_cfg.h conv_route / conv_route_multi / wgrad_route) over
+    every row and input combination under AddressSanitizer + UBSan."""
+    exe = tmp_path / "conv_route"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+           "-fno-sanitize-recover=all", str(HERE / "native" / "conv_route.cpp"), "-o", str(exe)]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.splitlines()[-1] == "ok", r.stdout
+
+
 ROOT = HERE.parent
 
 
