@@ -615,6 +615,35 @@ void cross_entropy_smooth(at::Tensor logits, at::Tensor labels, at::Tensor rowlo
                            cur_stream());
 }
 
+// Mixed-target cross-entropy: ya, yb int64 [B], lam float32 [B] (the weight of ya)
+void cross_entropy_mix(at::Tensor logits, at::Tensor ya, at::Tensor yb, at::Tensor lam,
+                       at::Tensor rowloss, at::Tensor loss, c10::optional<at::Tensor> dlogits,
+                       double scale, double eps) {
+  check_act(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2, "logits: (B, C)");
+  for (const at::Tensor* y : {&ya, &yb})
+    TORCH_CHECK(y->scalar_type() == at::kLong && y->numel() == logits.size(0) && y->is_cuda() &&
+                y->is_contiguous() && y->device() == logits.device(),
+                "labels: contiguous int64 [B] on the device of logits");
+  TORCH_CHECK(lam.scalar_type() == at::kFloat && lam.numel() == logits.size(0) && lam.is_cuda() &&
+              lam.is_contiguous() && lam.device() == logits.device(),
+              "lam: contiguous float32 [B] on the device of logits");
+  TORCH_CHECK(eps >= 0.0 && eps <= 1.0, "label smoothing must be in [0, 1]");
+  TORCH_CHECK(logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(0) < (1ll << 31) &&
+              logits.size(1) < (1ll << 31), "logits: empty or too large");
+  TORCH_CHECK(rowloss.is_cuda() && rowloss.is_contiguous(), "rowloss: contiguous device tensor");
+  CHECK_F32(rowloss); CHECK_F32(loss);
+  TORCH_CHECK(rowloss.numel() >= logits.size(0) && loss.numel() >= 1);
+  if (dlogits.has_value()) { check_act(*dlogits, "dlogits"); TORCH_CHECK(dlogits->sizes() == logits.sizes() && is_bf16(*dlogits) == is_bf16(logits)); }
+  const DeviceGuard guard(logits.device());
+  dm::cross_entropy_mix(logits.data_ptr(), (const long long*)ya.data_ptr(),
+                        (const long long*)yb.data_ptr(), lam.data_ptr<float>(),
+                        rowloss.data_ptr<float>(), loss.data_ptr<float>(),
+                        dlogits.has_value() ? dlogits->data_ptr() : nullptr, logits.size(0),
+                        logits.size(1), (float)scale, (float)eps, -100, is_bf16(logits),
+                        cur_stream());
+}
+
 // counts: int64[3] = {n, top-1 hits, top-k hits}; loss: float64[1]; both accumulate
 void eval_metrics(at::Tensor logits, at::Tensor labels, at::Tensor rowloss, at::Tensor rowrank,
                   int64_t k, at::Tensor counts, at::Tensor loss) {
@@ -653,12 +682,18 @@ std::array<int64_t, 4> aug_nhwc(const at::Tensor& t, const char* name) {
   return {t.size(0), t.size(1), t.size(2), c3};
 }
 
-// Gather + crop / resize / flip of a batch (csrc/augment.hip): out[b] = transform(params[b],
-// images[idx[b]]).  No allocation, no synchronisation.
-void augment_apply(at::Tensor images, at::Tensor idx, at::Tensor params, at::Tensor out) {
+// What augment_apply and augment_mix_apply check of their common arguments; the sizes of the
+// (N,H,W,C) views of images and out
+struct AugArgs {
+  std::array<int64_t, 4> is, os;
+  int64_t B;
+  int dtype;
+};
+AugArgs aug_check(const at::Tensor& images, const at::Tensor& idx, const at::Tensor& params,
+                  const at::Tensor& out, const char* fn) {
   CHECK_CUDA(images); CHECK_CUDA(idx); CHECK_CUDA(params); CHECK_CUDA(out);
   TORCH_CHECK(images.device() == idx.device() && images.device() == params.device() &&
-              images.device() == out.device(), "augment_apply: tensors on different devices");
+              images.device() == out.device(), fn, ": tensors on different devices");
   const auto st = images.scalar_type();
   TORCH_CHECK(st == at::kByte || st == at::kFloat || st == at::kBFloat16,
               "images must be uint8, float32 or bfloat16");
@@ -684,11 +719,35 @@ void augment_apply(at::Tensor images, at::Tensor idx, at::Tensor params, at::Ten
   const int64_t in_bytes = is[0] * is[1] * is[2] * is[3] * esz;
   const int64_t out_bytes = B * os[1] * os[2] * os[3] * esz;
   TORCH_CHECK(ob + out_bytes <= ib || ib + in_bytes <= ob, "out must not alias images");
-  if (B == 0) return;
+  return {is, os, B, st == at::kByte ? 0 : st == at::kFloat ? 1 : 2};
+}
+
+// Gather + crop / resize / flip of a batch (csrc/augment.hip): out[b] = transform(params[b],
+// images[idx[b]]).  No allocation, no synchronisation.
+void augment_apply(at::Tensor images, at::Tensor idx, at::Tensor params, at::Tensor out) {
+  const AugArgs a = aug_check(images, idx, params, out, "augment_apply");
+  if (a.B == 0) return;
   const DeviceGuard guard(images.device());
   dm::augment_apply(images.data_ptr(), (const long long*)idx.data_ptr(), params.data_ptr<int>(),
-                    out.data_ptr(), is[0], (int)is[1], (int)is[2], (int)is[3], (int)B, (int)os[1],
-                    (int)os[2], st == at::kByte ? 0 : st == at::kFloat ? 1 : 2, cur_stream());
+                    out.data_ptr(), a.is[0], (int)a.is[1], (int)a.is[2], (int)a.is[3], (int)a.B,
+                    (int)a.os[1], (int)a.os[2], a.dtype, cur_stream());
+}
+
+// The same with mixup / CutMix (csrc/augment_mix.hip): mix int32 [B,4] = partner, L, xbox, ybox.
+void augment_mix_apply(at::Tensor images, at::Tensor idx, at::Tensor params, at::Tensor mix,
+                       at::Tensor out) {
+  const AugArgs a = aug_check(images, idx, params, out, "augment_mix_apply");
+  CHECK_CUDA(mix);
+  TORCH_CHECK(mix.device() == images.device(), "augment_mix_apply: tensors on different devices");
+  TORCH_CHECK(mix.scalar_type() == at::kInt && mix.dim() == 2 && mix.size(0) == a.B &&
+              mix.size(1) == 4 && mix.is_contiguous(), "mix must be int32 [B,4]");
+  CHECK_ALIGN16(mix);
+  if (a.B == 0) return;
+  const DeviceGuard guard(images.device());
+  dm::augment_mix_apply(images.data_ptr(), (const long long*)idx.data_ptr(),
+                        params.data_ptr<int>(), mix.data_ptr<int>(), out.data_ptr(), a.is[0],
+                        (int)a.is[1], (int)a.is[2], (int)a.is[3], (int)a.B, (int)a.os[1],
+                        (int)a.os[2], a.dtype, cur_stream());
 }
 
 // One LeNet training step (csrc/lenet_fused.hip).  w: conv1.w, conv1.b, conv2.w, conv2.b,
@@ -847,9 +906,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cross_entropy", &cross_entropy);
   m.def("argmax_count", &argmax_count);
   m.def("cross_entropy_smooth", &cross_entropy_smooth);
+  m.def("cross_entropy_mix", &cross_entropy_mix);
   m.def("eval_metrics", &eval_metrics);
   m.def("spin_us", &spin_us);
   m.def("augment_apply", &augment_apply);
+  m.def("augment_mix_apply", &augment_mix_apply);
   m.def("lenet_fused_step", &lenet_fused_step, "one fused LeNet training step (2 dispatches)",
         py::arg("x"), py::arg("labels"), py::arg("w"), py::arg("rec"), py::arg("cslab"),
         py::arg("rowloss"), py::arg("grad"), py::arg("off"), py::arg("p"), py::arg("mom"),

@@ -97,6 +97,10 @@ void argmax_count(const void* logits, const long long* labels, int B, int C,
 void cross_entropy_smooth(const void* logits, const long long* labels, float* rowloss, float* loss,
                           void* dlogits, int B, int C, float scale, float eps, int ignore_index,
                           bool bf16, hipStream_t st);
+// mixed-target cross-entropy: the target of a row is lam*smooth(ya) + (1-lam)*smooth(yb)
+void cross_entropy_mix(const void* logits, const long long* ya, const long long* yb,
+                       const float* lam, float* rowloss, float* loss, void* dlogits, int B, int C,
+                       float scale, float eps, int ignore_index, bool bf16, hipStream_t st);
 // per-row NLL + label rank (B floats / B ints of scratch), then counts[3] = {n, top-1 hits,
 // top-k hits} and loss[1] (float64 sum) updated in fixed order
 void eval_metrics(const void* logits, const long long* labels, float* rowloss, int* rowrank, int B,
@@ -107,6 +111,11 @@ void spin_us(double us, hipStream_t st);
 void augment_apply(const void* images, const long long* idx, const int* params, void* out,
                    long long N, int H, int W, int C, int B, int OH, int OW, int dtype,
                    hipStream_t st);
+// augment_mix.hip: the same launch with mixup / CutMix: mix int32 [B,4] = partner, L, xbox, ybox
+// (16-B aligned); sample b is blended with, or has a box pasted from, batch row `partner`
+void augment_mix_apply(const void* images, const long long* idx, const int* params, const int* mix,
+                       void* out, long long N, int H, int W, int C, int B, int OH, int OW,
+                       int dtype, hipStream_t st);
 // lenet_fused.hip: the whole LeNet training step in 2 dispatches
 int lenet_record_floats();
 int lenet_slab_floats();

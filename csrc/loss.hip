@@ -129,6 +129,54 @@ __global__ void __launch_bounds__(256) ce_smooth_fwd_bwd_kernel(
   }
 }
 
+// Mixed-target cross-entropy (mixup / CutMix), the smoothed kernel with two labels per row: the
+// target is lam*smooth(ya) + (1-lam)*smooth(yb), so with t = lam*x_ya + (1-lam)*x_yb
+//   rowloss = (1-eps)*(lse - t) + eps*(lse - mean_c x_c)
+//   dlogits = (softmax - (1-eps)*(lam*[c==ya] + (1-lam)*[c==yb]) - eps/C) * scale
+// (ya == yb gives weight 1).  A row is valid iff both labels are in [0,C) and neither is
+// ignore_index; an invalid row has loss 0 and zero gradient, and its labels index nothing.
+template <typename T>
+__global__ void __launch_bounds__(256) ce_mix_fwd_bwd_kernel(
+    const T* __restrict__ logits, const long long* __restrict__ ya,
+    const long long* __restrict__ yb, const float* __restrict__ lam, float* __restrict__ rowloss,
+    T* __restrict__ dlogits, int B, int C, float scale, float eps, int ignore_index) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= B) return;
+  const T* x = logits + (long long)row * C;
+  float m = -INFINITY, sx = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float v = ldv(x, c);
+    m = fmaxf(m, v);
+    sx += v;
+  }
+  m = wave_max(m);
+  sx = wave_sum(sx);
+  float s = 0.f;
+  for (int c = lane; c < C; c += 64) s += __expf(ldv(x, c) - m);
+  s = wave_sum(s);
+  const float lse = m + __logf(s);
+  const long long a = ya[row], b = yb[row];
+  const bool valid = a != ignore_index && a >= 0 && a < C && b != ignore_index && b >= 0 && b < C;
+  const float la = lam[row], lb = 1.f - la;
+  const float uni = eps / (float)C;
+  if (lane == 0) {
+    const float t = valid ? la * ldv(x, a) + lb * ldv(x, b) : 0.f;
+    rowloss[row] = valid ? (1.f - eps) * (lse - t) + eps * (lse - sx / (float)C) : 0.f;
+  }
+  if (dlogits) {
+    T* d = dlogits + (long long)row * C;
+    const float inv = 1.f / s;
+    const float wa = (1.f - eps) * la, wb = (1.f - eps) * lb;
+    for (int c = lane; c < C; c += 64) {
+      const float hot = (c == a ? wa : 0.f) + (c == b ? wb : 0.f);
+      float g = valid ? (__expf(ldv(x, c) - m) * inv - hot - uni) * scale : 0.f;
+      if constexpr (sizeof(T) == 4) d[c] = g;
+      else d[c] = f2bf(g);
+    }
+  }
+}
+
 // Evaluation metrics, one pass per batch.  Per row: the (unsmoothed) NLL and the label's rank
 //   rank = #{c : x_c > x_y} + #{c < y : x_c == x_y}
 // so that the row hits at k iff rank < k (k = 1: argmax_count_kernel's first-index rule).  A
@@ -243,6 +291,21 @@ void cross_entropy_smooth(const void* logits, const long long* labels, float* ro
     ce_smooth_fwd_bwd_kernel<float><<<grid, 256, 0, st>>>((const float*)logits, labels, rowloss,
                                                           (float*)dlogits, B, C, scale, eps,
                                                           ignore_index);
+  sum_scale_kernel<<<1, 256, 0, st>>>(rowloss, B, scale, loss);
+}
+
+void cross_entropy_mix(const void* logits, const long long* ya, const long long* yb,
+                       const float* lam, float* rowloss, float* loss, void* dlogits, int B, int C,
+                       float scale, float eps, int ignore_index, bool bf16, hipStream_t st) {
+  const int grid = (B + 3) / 4;
+  if (bf16)
+    ce_mix_fwd_bwd_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)logits, ya, yb, lam, rowloss,
+                                                        (bf16_t*)dlogits, B, C, scale, eps,
+                                                        ignore_index);
+  else
+    ce_mix_fwd_bwd_kernel<float><<<grid, 256, 0, st>>>((const float*)logits, ya, yb, lam, rowloss,
+                                                       (float*)dlogits, B, C, scale, eps,
+                                                       ignore_index);
   sum_scale_kernel<<<1, 256, 0, st>>>(rowloss, B, scale, loss);
 }
 

@@ -7,7 +7,9 @@ dataset lives on the device (MNIST is 188 MB fp32 — nothing against 288 GB of
 HBM3E) and a batch is one ``index_select`` gather driven by the sampler's index
 list, which is itself uploaded once per epoch.  With a ``transform``
 (:class:`~dmlab.data.augment.DeviceAugment`) the gather happens inside the augmentation
-kernel instead, driven by the same index list plus a per-sample parameter table.
+kernel instead, driven by the same index list plus a per-sample parameter table.  With a
+``mix`` (:class:`~dmlab.data.mix.DeviceMix`) on top, that launch also blends or pastes each
+sample's partner, and the batch's target is a :class:`~dmlab.nn.MixTarget`.
 """
 from __future__ import annotations
 
@@ -76,9 +78,14 @@ class DeviceCursor:
 
 class DeviceLoader:
     def __init__(self, dataset, batch_size: int, sampler=None, shuffle: bool = False,
-                 drop_last: bool = False, seed: int = 0, device=None, transform=None):
+                 drop_last: bool = False, seed: int = 0, device=None, transform=None,
+                 mix=None):
+        if mix is not None and transform is None:
+            raise ValueError("DeviceLoader: mix needs a transform (the mixing runs inside the "
+                             "augmentation kernel; DeviceAugment.pad_crop(0) is the identity)")
         self.dataset = dataset
         self.transform = transform
+        self.mix = mix
         self.batch_size = int(batch_size)
         self.sampler = sampler
         self.shuffle = shuffle
@@ -119,16 +126,31 @@ class DeviceLoader:
     def _device_indices_params(self):
         """The epoch's index list and the transform's parameter table for exactly those
         indices (computed on the host once per epoch), uploaded the same way."""
+        return self._upload(*self._host_tables())[:2]
+
+    def _host_tables(self):
+        """Host tensors: the epoch's index list, the transform's table and, with ``mix``, the
+        mix table and label weights of the list cut into this loader's batches."""
         idx = self._indices()
-        par = self.transform.params(idx, self.epoch, size=image_size(self.dataset.images))
+        size = image_size(self.dataset.images)
+        tabs = (idx, self.transform.params(idx, self.epoch, size=size))
+        if self.mix is not None:
+            tabs += self.mix.epoch_params(idx, self.epoch, self.transform.out_size(size),
+                                          self.batch_size)
+        return tabs
+
+    def _upload(self, *tabs):
         if self.device.type == "cuda":
-            return (idx.pin_memory().to(self.device, non_blocking=True),
-                    par.pin_memory().to(self.device, non_blocking=True))
-        return idx.to(self.device), par.to(self.device)
+            return tuple(t.pin_memory().to(self.device, non_blocking=True) for t in tabs)
+        return tuple(t.to(self.device) for t in tabs)
 
     def _iter_transformed(self):
         """(augmented images, labels) batches: the transform gathers the rows itself, and
-        every batch is a fresh tensor (a consumer may keep it until its backward pass)."""
+        every batch is a fresh tensor (a consumer may keep it until its backward pass).  With
+        ``mix`` the labels are a MixTarget and the batch is still one launch."""
+        if self.mix is not None:
+            yield from self._iter_mixed()
+            return
         idx, par = self._device_indices_params()
         n = idx.numel()
         bs = self.batch_size
@@ -137,6 +159,21 @@ class DeviceLoader:
         for s in range(0, stop, bs):
             sl = idx[s: s + bs]
             yield self.transform.apply(im, sl, par[s: s + bs]), lb.index_select(0, sl)
+
+    def _iter_mixed(self):
+        from dmlab.nn.loss import MixTarget
+
+        idx, par, mix, lam = self._upload(*self._host_tables())
+        n = idx.numel()
+        bs = self.batch_size
+        stop = (n // bs) * bs if self.drop_last else n
+        im, lb = self.dataset.images, self.dataset.labels
+        for s in range(0, stop, bs):
+            sl, mx = idx[s: s + bs], mix[s: s + bs]
+            ya = lb.index_select(0, sl)
+            yb = ya.index_select(0, mx[:, 0].long())  # the table's partners are in [0, B)
+            yield (self.mix.apply(self.transform, im, sl, par[s: s + bs], mx),
+                   MixTarget(ya, yb, lam[s: s + bs]))
 
     def __iter__(self):
         if self.transform is not None:

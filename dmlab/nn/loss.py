@@ -8,10 +8,16 @@ by the incoming gradient.  CPU tensors use ``F.cross_entropy``.
 ResNet recipes use ε = 0.1): a second kernel of the same shape, one extra row sum, the
 same two launches.  ε = 0 is the plain kernel, untouched.
 
+A :class:`MixTarget` (two labels and the weight of the first per row, what mixup / CutMix
+produce) trains against ``lam·smooth(ya) + (1−lam)·smooth(yb)``: a third kernel of the same
+shape.  An int64 label tensor takes the paths above, untouched.
+
 :class:`EvalMetrics` keeps top-1 / top-k hits and the test loss in a device-resident
 state: one kernel pair per batch, one device-to-host read per evaluation.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -65,6 +71,57 @@ class _SmoothCEFn(torch.autograd.Function):
         return d * g.to(d.dtype), None, None
 
 
+class MixTarget(NamedTuple):
+    """The target of a mixed batch: row ``i`` is ``lam[i]`` of class ``labels[i]`` and
+    ``1 - lam[i]`` of class ``partner_labels[i]`` (int64 [B], int64 [B], float32 [B])."""
+
+    labels: torch.Tensor
+    partner_labels: torch.Tensor
+    lam: torch.Tensor
+
+
+class _MixCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, ya, yb, lam, eps):
+        from dmlab.ops._native import lib
+
+        logits = logits.contiguous()
+        B = logits.shape[0]
+        rowloss = torch.empty(B, device=logits.device, dtype=torch.float32)
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        need = ctx.needs_input_grad[0]
+        dlogits = torch.empty_like(logits) if need else None
+        lib().cross_entropy_mix(logits, ya.contiguous(), yb.contiguous(),
+                                lam.to(torch.float32).contiguous(), rowloss, loss, dlogits,
+                                1.0 / B, eps)
+        ctx.save_for_backward(dlogits if need else None)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (d,) = ctx.saved_tensors
+        if d is None:
+            return None, None, None, None, None
+        return d * g.to(d.dtype), None, None, None, None
+
+
+def _mix_cross_entropy_host(logits, target: MixTarget, eps: float, ignore_index: int = -100):
+    """The mixed loss from ``F.cross_entropy(..., reduction="none")`` terms; a row with an
+    invalid label in either slot has loss 0, and the mean is over all B rows."""
+    x = logits.float() if logits.dtype != torch.float32 else logits
+    B, C = x.shape
+    ya, yb = target.labels, target.partner_labels
+    valid = ((ya != ignore_index) & (ya >= 0) & (ya < C)
+             & (yb != ignore_index) & (yb >= 0) & (yb < C))
+    la = F.cross_entropy(x, torch.where(valid, ya, torch.zeros_like(ya)), reduction="none",
+                         label_smoothing=eps)
+    lb = F.cross_entropy(x, torch.where(valid, yb, torch.zeros_like(yb)), reduction="none",
+                         label_smoothing=eps)
+    lam = target.lam.to(torch.float32)
+    row = torch.where(valid, lam * la + (1.0 - lam) * lb, torch.zeros_like(la))
+    return row.sum() / B
+
+
 def _check_smoothing(eps) -> float:
     eps = float(eps)
     if not 0.0 <= eps <= 1.0:
@@ -73,7 +130,13 @@ def _check_smoothing(eps) -> float:
 
 
 def cross_entropy(logits, labels, label_smoothing=0.0):
+    """Mean cross-entropy of ``logits`` (B, C) against int64 labels [B] or a
+    :class:`MixTarget`."""
     eps = _check_smoothing(label_smoothing)
+    if isinstance(labels, MixTarget):
+        if logits.is_cuda:
+            return _MixCEFn.apply(logits, labels.labels, labels.partner_labels, labels.lam, eps)
+        return _mix_cross_entropy_host(logits, labels, eps)
     if logits.is_cuda:
         if eps == 0.0:
             return _CEFn.apply(logits, labels)

@@ -20,7 +20,7 @@ import json
 
 import torch
 
-from dmlab.data import DeviceAugment, DeviceLoader, MySampler, ShardSampler, load_mnist
+from dmlab.data import DeviceAugment, DeviceLoader, DeviceMix, MySampler, ShardSampler, load_mnist
 from dmlab.models import Net, ResNet18
 from dmlab.nn import CrossEntropyLoss
 from dmlab.optim import LARS, SGD, WarmupPolyLR
@@ -82,6 +82,18 @@ def parse_args(argv=None):
     p.add_argument("--aug-flip", type=float, default=None,
                    help="horizontal-flip probability (default 0.5 for resnet18, 0 for lenet)")
     p.add_argument("--aug-seed", type=int, default=0)
+    p.add_argument("--mixup", type=float, default=0.0, metavar="A",
+                   help="on-device mixup: each sample blended with the one at the mirrored "
+                        "batch position, weight ~ Beta(A, A) drawn per (--aug-seed, dataset "
+                        "index, epoch); 0 = off.  The loss takes both labels")
+    p.add_argument("--cutmix", type=float, default=0.0, metavar="A",
+                   help="on-device CutMix: a box of the mirrored sample pasted in, area "
+                        "fraction ~ 1 - Beta(A, A); 0 = off.  Like --augment, mixing needs the "
+                        "layer-wise loop, and evaluation is unmixed")
+    p.add_argument("--mix-prob", type=float, default=1.0, metavar="P",
+                   help="probability that a sample is mixed at all")
+    p.add_argument("--mix-switch-prob", type=float, default=0.5, metavar="P",
+                   help="with --mixup and --cutmix: probability that a mixed sample is CutMix")
     p.add_argument("--bucket-mb", type=float, default=25.0)
     p.add_argument("--allreduce", default="auto", choices=["auto", "rccl", "xgmi"],
                    help="small-bucket all-reduce: RCCL ring or the one-shot xGMI kernel.  At "
@@ -157,6 +169,17 @@ def main(argv=None):
     if a.fused == "1" and a.augment != "none":
         raise SystemExit("--fused 1 reads the dataset rows inside the fused LeNet step; "
                          "--augment needs the layer-wise loop (--fused auto or 0)")
+    mixing = a.mixup != 0 or a.cutmix != 0
+    if a.fused == "1" and mixing:
+        raise SystemExit("--fused 1 reads the dataset rows inside the fused LeNet step; "
+                         "--mixup and --cutmix need the layer-wise loop (--fused auto or 0)")
+    mix = None
+    if mixing:
+        try:
+            mix = DeviceMix(a.mixup, a.cutmix, prob=a.mix_prob, switch_prob=a.mix_switch_prob,
+                            seed=a.aug_seed)
+        except ValueError as e:
+            raise SystemExit(f"--mixup / --cutmix: {e}")
     aug = None
     if a.augment != "none":
         if a.aug_flip is None:
@@ -218,11 +241,13 @@ def main(argv=None):
     # keeps fp32)
     act = torch.bfloat16 if (a.dtype == "bf16" and a.model == "lenet" and dev.type == "cuda") \
         else None
-    if aug is None:
+    if aug is None and mix is None:
         loader = DeviceLoader(train_set.to(dev, dtype=act), a.batch_size, sampler=sampler)
     else:  # the augmentation kernel reads channel-innermost rows
+        # mixing runs inside the augmentation launch: without --augment, the identity transform
+        tf = aug if aug is not None else DeviceAugment.pad_crop(0, flip=0.0, seed=a.aug_seed)
         loader = DeviceLoader(train_set.to(dev, dtype=act, memory_format=torch.channels_last),
-                              a.batch_size, sampler=sampler, transform=aug)
+                              a.batch_size, sampler=sampler, transform=tf, mix=mix)
     if a.optimizer == "lars":
         opt = LARS(model.parameters(), lr=a.lr, momentum=a.momentum,
                    weight_decay=a.weight_decay, trust_coefficient=a.trust_coef)
@@ -269,7 +294,7 @@ def main(argv=None):
     fused = a.fused == "1" or (a.fused == "auto" and a.model == "lenet" and dev.type == "cuda"
                                and a.dp == "ddp" and a.optimizer == "sgd"
                                and a.warmup_steps == 0 and a.label_smoothing == 0
-                               and aug is None)
+                               and aug is None and mix is None)
     if fused:
         if a.model != "lenet" or dev.type != "cuda" or a.dp != "ddp":
             raise SystemExit("--fused 1 needs --model lenet on a GPU with --dp ddp")
@@ -300,6 +325,8 @@ def main(argv=None):
         stats["label_smoothing"] = a.label_smoothing
     if aug is not None:
         stats.update(augment=a.augment, aug_seed=a.aug_seed, aug_flip=a.aug_flip)
+    if mix is not None:
+        stats.update(mixup=a.mixup, cutmix=a.cutmix, mix_prob=a.mix_prob)
     print("Training time: {}".format(stats["train_time"]))
     if rank == 0:
         print("Throughput: {:.1f} samples/s (whole job, {} rank{})".format(
