@@ -20,7 +20,8 @@ from dmlab.nn.program import Program
 
 
 class ResNet18(Program):
-    # the s2d stem packing gathers a loader batch by index itself (no batch copy)
+    # both stems (the fused K-dense kernel and the s2d packing) gather a loader batch by index
+    # themselves (no batch copy)
     accepts_gathered = True
 
     def __init__(self, num_classes: int = 1000, in_channels: int = 3,

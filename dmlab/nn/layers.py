@@ -164,14 +164,21 @@ class ConvBN(Layer):
         """raw: return the conv output y un-normalised (BN scale/shift left in ctx for the
         consumer); pre=(scale, shift): x is a raw conv output to be consumed as
         relu(x*scale + shift) — the BN-apply of the previous layer fused into this conv."""
-        from dmlab.ops import convbn as CB
+        from dmlab.ops import convbn as CB, stem
 
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and getattr(x, "_dm_nhwc", False)):
+            # a raw image batch: this is a first layer
+            assert residual is None and not raw and pre is None, \
+                "a first layer (raw image input) takes no residual, raw or pre"
+            return stem.stem_fwd(self, x, ctx, train)
         return CB.convbn_fwd(self, x, ctx, train, residual, raw=raw, pre=pre)
 
     def native_bwd(self, dy, ctx, need_dx, dx_add=None, dx_into=None, fused_skip=False,
                    red_for=None, phase=0, shortcut=None):
-        from dmlab.ops import convbn as CB
+        from dmlab.ops import convbn as CB, stem
 
+        if "stem" in ctx:  # the forward took the first-layer path: no data gradient
+            return stem.stem_bwd(self, dy, ctx)
         return CB.convbn_bwd(self, dy, ctx, need_dx, dx_add=dx_add, dx_into=dx_into,
                              fused_skip=fused_skip, red_for=red_for, phase=phase,
                              shortcut=shortcut)
@@ -191,6 +198,16 @@ class ConvBNPool(ConvBN):
 
         y = super().torch_forward(normalize_input(x, self.weight.dtype))  # u8 images: ImageNet norm
         return F.max_pool2d(y, self.pool_k, self.pool_s, self.pool_p)
+
+    def native_fwd(self, x, ctx, train):
+        from dmlab.ops import stem
+
+        return stem.stem_fwd(self, x, ctx, train)
+
+    def native_bwd(self, dy, ctx, need_dx):
+        from dmlab.ops import stem
+
+        return stem.stem_bwd(self, dy, ctx)
 
 
 class BasicBlock(Layer):

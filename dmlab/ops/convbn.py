@@ -12,12 +12,28 @@ Backward: BN backward (reduce + apply, also emitting the residual-branch grad) â
 Activations are plain contiguous ``[N, H, W, C]`` bf16 tensors.  Packed bf16
 weights ([Cout][KH][KW][Cpad] for forward, [Cin][KH][KW][Cout] for dgrad) are
 cached per layer and refreshed when the fp32 master changes.
+
+:func:`convbn_fwd` / :func:`convbn_bwd` serve interior layers (input already internal NHWC);
+a first layer (raw image input) goes through :mod:`dmlab.ops.stem`, which shares
+:func:`conv_stats`, :func:`bn_bwd` and :func:`launch_wgrad` with them.
+
+ctx of an interior ConvBN (written by convbn_fwd in training; readers in brackets):
+  x, y        conv input (un-normalised when ``pre`` is set) and output [bn_bwd, launch_wgrad,
+              _dgrad; y also _dgrad_red of the producing layer's data gradient]
+  mean, invstd, scale, shift   batch statistics (None in eval mode) and the BN affine
+              [bn_bwd, _dgrad_red; BasicBlock reads c1's scale / shift as c2's ``pre``]
+  pre         (scale, shift) of the previous BN when x is its raw conv output [launch_wgrad]
+  total       global element count under synchronized BatchNorm, else None [bn_bwd]
+  has_res     the forward added a residual [convbn_bwd: BN mode, the (dx, dres) return]
+  out, mask   with a residual: the output and, with ReLU, its 1-bit (out > 0) mask
+              [convbn_bwd modes 1 / 4, _dgrad_red, the fused skip add of the next dgrad]
+  pre_sums    left by _dgrad_red of the layer above: this BN's backward sums [convbn_bwd pops]
+  _bn_out     (dy, dres) between phase 1 and phase 2 of convbn_bwd
 """
 from __future__ import annotations
 
 import contextlib
 import math
-import os
 
 import torch
 
@@ -35,7 +51,6 @@ def _cpad(c):
 #     channels: v3 tiles 15 / 13 / 11 by the block-count rule below (256-row tiles lose
 #     there: one workgroup per CU exposes the staging latency).
 TILE_CFG = (15, 13, 11)
-_STEM_CFG = 60
 # The round-3 A/B switches (DMLAB_NO_PIPE / NO_RES64 / NO_FUSED_SKIP / NO_DGRAD_RED /
 # NO_WRES64 / WRES64_S / TAIL_WGRAD_FULL / WGRAD_BLOCKS / RES64_ADD_RED / STEM_CFG) are
 # settled and removed; their measurements stay in docs/KERNELS.md and profiles/.
@@ -207,174 +222,33 @@ def empty_nhwc(N, H, W, C, like):
     return _mark(torch.empty((N, H, W, C), device=like.device, dtype=torch.bfloat16))
 
 
-def use_s2d(layer, x):
-    """7x7/s2 stem on a small-channel input with even H, W -> space-to-depth 4x4/s1."""
-    return (layer.k == 7 and layer.stride == 2 and layer.padding == 3 and layer.cin <= 4
-            and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0)
-
-
-def packed_weights_s2d(layer):
-    prog = layer._prog
-    cache = getattr(layer, "_wcache_s2d", None)
-    if cache is None or cache[0] != prog._wver:
-        w = layer.weight.detach()
-        wf = torch.empty((layer.cout, 4, 4, _cpad(4 * layer.cin)), device=w.device,
-                         dtype=torch.bfloat16)
-        lib().pack_weights_s2d(w, wf)
-        cache = (prog._wver, wf)
-        object.__setattr__(layer, "_wcache_s2d", cache)
-    return cache[1]
-
-
-def packed_weights_stem(layer):
-    """[64][176] bf16 K-dense stem weights (k = ky*24 + kx*3 + c), cached per weight version."""
-    prog = layer._prog
-    cache = getattr(layer, "_wcache_k176", None)
-    if cache is None or cache[0] != prog._wver:
-        wk = cache[1] if cache is not None else torch.empty(
-            (64, 176), device=layer.weight.device, dtype=torch.bfloat16)
-        lib().stem_pack_weights(layer.weight.detach(), wk)
-        cache = (prog._wver, wk)
-        object.__setattr__(layer, "_wcache_k176", cache)
-    return cache[1]
-
-
-def _stem_image(x):
-    """(images, idx) of a stem input: a loader batch by index (dmlab.data.Gathered) or an
-    image tensor ((N,3,H,W) channels_last or (N,H,W,3)); None if it is neither."""
-    if not isinstance(x, torch.Tensor):
-        return x.images, x.idx
-    if x.dim() == 4 and x.shape[1] == 3 and not getattr(x, "_dm_nhwc", False):
-        if not x.is_contiguous(memory_format=torch.channels_last):
-            x = x.contiguous(memory_format=torch.channels_last)
-        return x, None
-    return None
-
-
-_STEM_FUSED_DEFAULT = "1"  # GPU-validated (tests/test_stem_fused.py); bench A/B +1.9 %
-
-
-def stem_fused_ok(layer, x):
-    """The K-dense fused stem (csrc/stem_fused.hip) serves this layer and input:
-    7x7/s2/p3 conv 3 -> 64 + BN + ReLU + 3x3/s2/p1 max-pool, on a raw fp32 / bf16 / u8 image
-    batch whose size the kernel supports, BN in training mode or eval (not eval-BN with
-    gradients).  DMLAB_STEM_FUSED=0 selects the space-to-depth path (A/B)."""
-    if os.environ.get("DMLAB_STEM_FUSED", _STEM_FUSED_DEFAULT) == "0":
-        return False
-    if not (getattr(layer, "pool_k", 0) == 3 and layer.pool_s == 2 and layer.pool_p == 1
-            and layer.k == 7 and layer.stride == 2 and layer.padding == 3 and layer.cin == 3
-            and layer.cout == 64 and layer.relu):
-        return False
-    im = _stem_image(x)
-    if im is None:
-        return False
-    img = im[0]
-    if img.dtype not in (torch.float32, torch.bfloat16, torch.uint8) or not img.is_cuda:
-        return False
-    H, W = (img.shape[2], img.shape[3]) if img.shape[1] == 3 else (img.shape[1], img.shape[2])
-    return bool(lib().stem_fused_supported(H, W))
-
-
-def _bn_finalize(L, layer, stats, T, M, scale, shift, mean, invstd, work):
-    """Statistics slab [T][2C] -> scale / shift / mean / invstd + the running statistics.
-    Per-rank BatchNorm: one finalize over this rank's M elements, returns None.  Synchronized
-    (dmlab.nn.syncbn): local float64 row -> all-gather -> merge in rank order; returns the
+def _bn_finalize(L, layer, stats, T, M):
+    """Statistics slab [T][2C] -> (scale, shift, mean, invstd, total) + the running statistics;
+    ``stats`` None (eval-mode BN): scale / shift from the running statistics, the rest None.
+    Per-rank BatchNorm: one finalize over this rank's M elements, total None.  Synchronized
+    (dmlab.nn.syncbn): local float64 row -> all-gather -> merge in rank order; total is the
     global element count as a float64 device scalar (it never visits the host)."""
     g, b = layer.bn_weight.detach(), layer.bn_bias.detach()
+    C = layer.cout
+    f32 = dict(device=g.device, dtype=torch.float32)
+    scale, shift = torch.empty(C, **f32), torch.empty(C, **f32)
+    if stats is None:
+        L.bn_eval_coeffs(g, b, layer.running_mean, layer.running_var, layer.eps, scale, shift)
+        return scale, shift, None, None, None
+    mean, invstd, work = torch.empty(C, **f32), torch.empty(C, **f32), torch.empty(512 * C, **f32)
     sync = layer._sync_bn
     if sync is None:
         L.bn_stats_finalize(stats, T, float(M), g, b, layer.running_mean, layer.running_var,
                             layer.momentum, layer.eps, scale, shift, mean, invstd, work,
                             layer.num_batches_tracked)
-        return None
-    C = layer.cout
+        return scale, shift, mean, invstd, None
     row = torch.empty(2 * C + 1, device=stats.device, dtype=torch.float64)
     L.bn_sync_local(stats, T, float(M), C, row, work)
     rows = sync.gather_rows(row)
     total = torch.empty(1, device=stats.device, dtype=torch.float64)
     L.bn_sync_finalize(rows, g, b, layer.running_mean, layer.running_var, layer.momentum,
                        layer.eps, scale, shift, mean, invstd, layer.num_batches_tracked, total)
-    return total
-
-
-def _stem_fused_fwd(layer, x, ctx, train):
-    """Fused stem forward: pooled BN-input extremum + window codes + BN statistics in one
-    kernel, then BN + ReLU on the pooled tensor.  The conv output is never written."""
-    from dmlab.data import input_affine
-
-    L = lib()
-    img, idx = _stem_image(x)
-    B = idx.numel() if idx is not None else img.shape[0]
-    H, W = (img.shape[2], img.shape[3]) if img.shape[1] == 3 else (img.shape[1], img.shape[2])
-    PH, PW = H // 4, W // 4
-    dev = img.device
-    nsc, nbi = input_affine(img.dtype)
-    wk = packed_weights_stem(layer)
-    pext = empty_nhwc(B, PH, PW, 64, img)
-    code = torch.empty((B, PH, PW, 32), device=dev, dtype=torch.uint8)
-    grid = L.stem_fused_grid(B)
-    f32 = dict(device=dev, dtype=torch.float32)
-    scale = torch.empty(64, **f32)
-    shift = torch.empty(64, **f32)
-    use_batch = layer.training
-    stats = torch.empty(grid * 128, **f32) if use_batch else None
-    L.stem_fwd_fused(img, idx, nsc, nbi, wk, layer.bn_weight.detach(), pext, code, stats, grid)
-    M = B * (H // 2) * (W // 2)
-    total = None
-    if use_batch:
-        mean = torch.empty(64, **f32)
-        invstd = torch.empty(64, **f32)
-        work = torch.empty(256 * 2 * 64, **f32)
-        total = _bn_finalize(L, layer, stats, grid, M, scale, shift, mean, invstd, work)
-    else:
-        L.bn_eval_coeffs(layer.bn_weight.detach(), layer.bn_bias.detach(), layer.running_mean,
-                         layer.running_var, layer.eps, scale, shift)
-        mean = invstd = None
-    out = empty_nhwc(B, PH, PW, 64, img)
-    code4 = torch.empty((B, PH, PW, 32), device=dev, dtype=torch.uint8) if train else None
-    L.stem_pool_apply(pext, code if train else None, scale, shift, out, code4)
-    if train:
-        ctx.update(fused_stem=True, img=img, gidx=idx, nsc=nsc, nbi=nbi, wk=wk, yarg=pext,
-                   idx=code4, mean=mean, invstd=invstd, scale=scale, shift=shift, has_res=False,
-                   first=True, s2d=False, pre=None, y=pext, x=None, M=M, total=total)
-    return out
-
-
-def _stem_fused_bwd(layer, dout, ctx):
-    """Fused stem backward: BN-backward coefficients from the pooled-domain sums, then the
-    weight gradient of dy = a*dz + b*y + cc with y recomputed from the raw input (never
-    stored), reduced in fixed order into the OIHW gradient."""
-    L = lib()
-    dout = dout.contiguous()
-    pext, code = ctx["yarg"], ctx["idx"]
-    acc = 1.0 if layer.accumulate else 0.0
-    pre_sums = ctx.pop("pre_sums", None) or {}
-    if not pre_sums:
-        part = torch.empty(L.bn_bwd_rows(pext.numel() // 64, 64) * 2 * 64, device=dout.device,
-                           dtype=torch.float32)
-        rows = L.bn_bwd_reduce_masked(dout, pext, ctx["mean"], ctx["invstd"], ctx["scale"],
-                                      ctx["shift"], part)
-        pre_sums = dict(pre_slab=part, pre_rows=rows)
-    B = dout.shape[0]
-    grid = L.stem_fused_grid(B)
-    f32 = dict(device=dout.device, dtype=torch.float32)
-    work = torch.empty(L.bn_bwd_work(ctx["M"], 64), **f32)
-    dslab = torch.empty(L.stem_bwd_slab_len(grid), **f32)
-    sync_kw = {}
-    if ctx.get("total") is not None:
-        # synchronized BatchNorm: dgamma / dbeta from this rank's sums, the coefficients from
-        # the sums of every rank and the global count
-        sums = torch.empty(128, device=dout.device, dtype=torch.float64)
-        L.bn_bwd_sums(pre_sums["pre_slab"], pre_sums["pre_rows"], 64, layer.grad_slot("bn_weight"),
-                      layer.grad_slot("bn_bias"), acc, work, sums)
-        layer._sync_bn.reduce_sums(sums)
-        sync_kw = dict(sums=sums, total=ctx["total"])
-    L.stem_bwd_fused2(ctx["img"], ctx["gidx"], ctx["nsc"], ctx["nbi"], ctx["wk"], dout, code,
-                      ctx["mean"], ctx["invstd"], layer.bn_weight.detach(),
-                      layer.grad_slot("bn_weight"), layer.grad_slot("bn_bias"), acc,
-                      pre_sums["pre_slab"], pre_sums["pre_rows"], layer.grad_slot("weight"), acc,
-                      work, dslab, grid, **sync_kw)
-    return None
+    return scale, shift, mean, invstd, total
 
 
 def packed_weights(layer, need_wd=True):
@@ -436,46 +310,30 @@ def _materialise(x, pre):
     return out
 
 
-def convbn_fwd(layer, x, ctx, train, residual=None, raw=False, pre=None):
-    L = lib()
-    if (residual is None and not raw and pre is None and (layer.training or not train)
-            and stem_fused_ok(layer, x)):
-        return _stem_fused_fwd(layer, x, ctx, train)
-    gidx = None
-    if not isinstance(x, torch.Tensor):  # dmlab.data.Gathered: a loader batch by row index
-        if use_s2d(layer, x.images) and x.images.dtype in (torch.float32, torch.bfloat16):
-            x, gidx = x.images, x.idx  # the s2d packing below gathers the rows itself
-        else:
-            x = x.materialize()
-    first = not (x.dim() == 4 and getattr(x, "_dm_nhwc", False))
-    s2d = first and use_s2d(layer, x)
-    if s2d:
-        # stem as a 4x4/s1 conv over the space-to-depth input (pad 2 top/left, 1 bottom/right)
-        Nn, Cc, Hh, Ww = x.shape
-        if gidx is not None:
-            Nn = gidx.numel()
-        xs = empty_nhwc(Nn, Hh // 2, Ww // 2, _cpad(4 * Cc), x)
-        L.pack_input_s2d(x if x.dtype in (torch.float32, torch.bfloat16) else x.float(), xs, gidx)
-        x = xs
-        k, s, p = 4, 1, 2
-        OH, OW = Hh // 2, Ww // 2
-        wf = packed_weights_s2d(layer)
-    else:
-        x = as_nhwc(x, _cpad(layer.cin)) if first else x
-        k, s, p = layer.k, layer.stride, layer.padding
-        wf = None
-    N, H, W, C = x.shape
-    if not s2d:
-        OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+def conv_stats(L, layer, x, wf, k, s, p, cfg, pre_kw, OH, OW):
+    """Shared forward step (interior layers and dmlab.ops.stem): the conv, whose epilogue emits
+    the BN statistics slab in training mode, then the BN coefficients (_bn_finalize).
+    Returns y, scale, shift, mean, invstd, total."""
+    N, cout = x.shape[0], layer.cout
     M = N * OH * OW
-    cout = layer.cout
-    if wf is None:
-        wf, _ = packed_weights(layer, need_wd=train and not first)
     y = empty_nhwc(N, OH, OW, cout, x)
-    # s2d stem: the resident-weight stem kernel (60, csrc/conv_stem.hip) stages the weights
-    # and the input halo once per 256 pixels (the v3 128x64 tile, 16, re-stages one 4-tap
-    # K-slice per step: 382 TFLOP/s at batch 512, profiles/conv_stem_s2d_r1s4.jsonl)
-    cfg = _STEM_CFG if s2d else pick_cfg(M, cout, k, s, C, W=OW if (OH, OW) == (H, W) else 0)
+    T, stats = 0, None
+    if layer.training:
+        T = L.conv_stats_rows(M, cfg)
+        stats = torch.empty(T * 2 * cout, device=x.device, dtype=torch.float32)
+    L.conv_fwd(x, wf, y, stats, None, k, k, s, p, cfg, **pre_kw)
+    return (y,) + _bn_finalize(L, layer, stats, T, M)
+
+
+def convbn_fwd(layer, x, ctx, train, residual=None, raw=False, pre=None):
+    """Interior ConvBN forward: x is an internal NHWC bf16 tensor (module docstring: ctx)."""
+    L = lib()
+    k, s, p = layer.k, layer.stride, layer.padding
+    N, H, W, C = x.shape
+    OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    cout = layer.cout
+    wf, _ = packed_weights(layer, need_wd=train)
+    cfg = pick_cfg(N * OH * OW, cout, k, s, C, W=OW if (OH, OW) == (H, W) else 0)
     pre_kw = {}
     if pre is not None:
         # the halo tiles (layer 2) and the layer-1 kernel normalise y1 on the fly; for the
@@ -488,45 +346,14 @@ def convbn_fwd(layer, x, ctx, train, residual=None, raw=False, pre=None):
         else:  # not a halo-kernel shape: materialise the previous BN output
             x = _materialise(x, pre)
             pre = None
-    f32 = dict(device=x.device, dtype=torch.float32)
-    scale = torch.empty(cout, **f32)
-    shift = torch.empty(cout, **f32)
-    use_batch = layer.training
-    total = None
-    if use_batch:
-        T = L.conv_stats_rows(M, cfg)
-        stats = torch.empty(T * 2 * cout, **f32)
-        L.conv_fwd(x, wf, y, stats, None, k, k, s, p, cfg, **pre_kw)
-        mean = torch.empty(cout, **f32)
-        invstd = torch.empty(cout, **f32)
-        work = torch.empty(256 * 2 * cout, **f32)
-        total = _bn_finalize(L, layer, stats, T, M, scale, shift, mean, invstd, work)
-    else:
-        L.conv_fwd(x, wf, y, None, None, k, k, s, p, cfg, **pre_kw)
-        L.bn_eval_coeffs(layer.bn_weight.detach(), layer.bn_bias.detach(), layer.running_mean,
-                         layer.running_var, layer.eps, scale, shift)
-        mean = invstd = None
+    y, scale, shift, mean, invstd, total = conv_stats(L, layer, x, wf, k, s, p, cfg, pre_kw,
+                                                      OH, OW)
     if train:
         ctx.update(x=x, y=y, mean=mean, invstd=invstd, has_res=residual is not None,
-                   first=first, s2d=s2d, scale=scale, shift=shift, pre=pre, total=total)
+                   scale=scale, shift=shift, pre=pre, total=total)
     if raw:
         ctx["scale"], ctx["shift"] = scale, shift
         return y
-    pool = getattr(layer, "pool_k", 0)
-    if pool:
-        # fused BN + ReLU + max-pool: the BN output is never materialised
-        pk, ps, pp = layer.pool_k, layer.pool_s, layer.pool_p
-        PH, PW = (OH + 2 * pp - pk) // ps + 1, (OW + 2 * pp - pk) // ps + 1
-        out = empty_nhwc(N, PH, PW, cout, x)
-        idx = torch.empty((N, PH, PW, cout), device=x.device, dtype=torch.uint8)
-        # training: also keep y at each window's argmax, so the backward reduces the BN
-        # sums over the pooled grid (see bn_relu_maxpool_kernel)
-        yarg = empty_nhwc(N, PH, PW, cout, x) if (train and use_batch) else None
-        L.bn_relu_maxpool(y, scale, shift, out, idx, pk, ps, pp, yarg=yarg)
-        if train:
-            ctx["idx"] = idx
-            ctx["yarg"] = yarg
-        return out
     out = empty_nhwc(N, OH, OW, cout, x)
     # residual + ReLU in training: a 1-bit (out > 0) mask is the backward's ReLU mask source
     # (the residual is not kept; re-reading `out` would cost 16x the bytes)
@@ -610,15 +437,10 @@ def convbn_bwd(layer, dout, ctx, need_dx, dx_add=None, dx_into=None, fused_skip=
                   merge it, the projection's data gradient becomes a second K segment of parity
                   class (0,0) in THIS launch (dx written once, complete, so ``red_for`` applies
                   too) and shortcut["merged"] is set -- the caller then skips its dgrad"""
-    if ctx.get("fused_stem"):
-        return _stem_fused_bwd(layer, dout, ctx)
     L = lib()
-    x, y = ctx["x"], ctx["y"]
-    N, OH, OW, cout = y.shape
-    M = N * OH * OW
-    s2d = ctx.get("s2d", False)
-    k, s, p = (4, 1, 2) if s2d else (layer.k, layer.stride, layer.padding)
-    acc = 1.0 if layer.accumulate else 0.0
+    y = ctx["y"]
+    cout = y.shape[3]
+    k, s, p = layer.k, layer.stride, layer.padding
     # ("masked", dout, mask): the upstream gradient is dout * mask (a projection shortcut fed
     # the block's unmaterialised residual gradient); the BN backward's mode 4 applies exactly
     # that mask, so no ReLU of its own is involved
@@ -627,40 +449,8 @@ def convbn_bwd(layer, dout, ctx, need_dx, dx_add=None, dx_into=None, fused_skip=
         _, dout, in_mask = dout
         assert not layer.relu and not ctx["has_res"], "masked upstream gradient: linear BN only"
     dout = dout.contiguous()
-    pool = getattr(layer, "pool_k", 0)
-    if phase == 2:
-        assert not pool, "phase 2: a plain ConvBN"
-        work, pre_sums = None, {}
-    else:
-        work = torch.empty(L.bn_bwd_work(M, cout), device=y.device, dtype=torch.float32)
-        pre_sums = ctx.pop("pre_sums", None) or {}
-    if pool and ctx.get("yarg") is not None and not pre_sums:
-        # stem: Î£dz, Î£dzÂ·xÌ‚ over the pooled grid (pooled grad masked at the argmax, xÌ‚ from
-        # y at the argmax) -- reads 2 pooled-size tensors instead of y + grad + codes
-        Mp = ctx["yarg"].numel() // cout
-        part = torch.empty(L.bn_bwd_rows(Mp, cout) * 2 * cout, device=y.device,
-                           dtype=torch.float32)
-        rows = L.bn_bwd_reduce_masked(dout, ctx["yarg"], ctx["mean"], ctx["invstd"], ctx["scale"],
-                                      ctx["shift"], part)
-        pre_sums = dict(pre_slab=part, pre_rows=rows)
-    # synchronized BatchNorm (ctx["total"]: the global count of the forward's merge): the
-    # space-to-depth stem takes the unfused mode-3 backward below, which has the two stages
-    total = ctx.get("total")
-    stem_ok = (pool and s2d and pre_sums and ctx["first"] and not ctx["has_res"]
-               and total is None and L.stem_bwd_fused_supported(y, x))
-    if stem_ok:
-        # stem: BN-backward apply fused into the s2d weight gradient -- the full-resolution
-        # dy is never written (csrc/conv_stem.hip stem_wgrad_ws_kernel)
-        slab = torch.empty(L.stem_bwd_slab_floats(N, OH), device=y.device, dtype=torch.float32)
-        L.stem_bwd_fused(y, ctx["mean"], ctx["invstd"], layer.bn_weight.detach(),
-                         layer.grad_slot("bn_weight"), layer.grad_slot("bn_bias"), acc,
-                         ctx["scale"], ctx["shift"], dout, ctx["idx"], pre_sums["pre_slab"],
-                         pre_sums["pre_rows"], x, layer.cin, layer.grad_slot("weight"), acc,
-                         work, slab)
-        return None
-    if pool:
-        mode = 3       # dz gathered from the max-pool gradient, ReLU mask from y
-    elif in_mask is not None:
+    # 1. the BN mode
+    if in_mask is not None:
         mode = 4       # dz = dout * the residual block's 1-bit mask
     elif not layer.relu:
         mode = 0
@@ -669,15 +459,8 @@ def convbn_bwd(layer, dout, ctx, need_dx, dx_add=None, dx_into=None, fused_skip=
         mode = 4 if ctx.get("mask") is not None else 1
     else:
         mode = 2       # mask recomputed from y (no `out` read)
-    C = x.shape[3]
-    K = k * k * C
-    same = not s2d and (OH, OW) == tuple(x.shape[1:3])
-    # red_for is the stem (a pooled ConvBN) only for the first block's c1: the step's last conv
-    tail = red_for is not None and bool(getattr(red_for[0], "pool_k", 0))
-    even = OW if (not s2d and 2 * OH == x.shape[1] and 2 * OW == x.shape[2]) else 0
-    wcfg, S = _wgrad_plan(M, cout, K, k, s, C, W=OW if same else 0, rows=N * OH if same else 0,
-                          tail=tail, even=even)
     masked_res = fused_skip and ctx["has_res"] and mode == 4
+    # 2. BN backward, or phase 1's
     if phase == 2:
         dy, dres = ctx.pop("_bn_out")
         # allocated on the phase-1 stream, read here and on the weight-gradient stream
@@ -685,78 +468,112 @@ def convbn_bwd(layer, dout, ctx, need_dx, dx_add=None, dx_into=None, fused_skip=
         if dres is not None:
             dres.record_stream(torch.cuda.current_stream())
     else:
-        dy = empty_nhwc(N, OH, OW, cout, y)
-        dres = empty_nhwc(N, OH, OW, cout, y) if (ctx["has_res"] and not masked_res) else None
-        bn_args = (None if pool else dout, ctx.get("out"), y, ctx["mean"], ctx["invstd"],
-                   layer.bn_weight.detach(), layer.grad_slot("bn_weight"),
-                   layer.grad_slot("bn_bias"), acc, mode, ctx["scale"], ctx["shift"],
-                   dout if pool else None, ctx.get("idx"),
-                   getattr(layer, "pool_k", 3), getattr(layer, "pool_s", 2),
-                   getattr(layer, "pool_p", 1), dy, dres, work)
-        bn_mask = in_mask if in_mask is not None else ctx.get("mask")
-        if total is None:
-            L.bn_backward(*bn_args, mask=bn_mask, **pre_sums)
-        else:
-            # stage "sums": this rank's Î£dz, Î£dzÂ·xÌ‚ (reduced here or taken from pre_sums) ->
-            # dgamma / dbeta and a float64 row; all-reduce; stage "apply": the coefficients
-            # from the global sums and count, then the same apply kernels
-            sums = torch.empty(2 * cout, device=y.device, dtype=torch.float64)
-            L.bn_backward(*bn_args, mask=bn_mask, stage=1, sums=sums, **pre_sums)
-            layer._sync_bn.reduce_sums(sums)
-            L.bn_backward(*bn_args, mask=bn_mask, stage=2, sums=sums, total=total)
+        work = torch.empty(L.bn_bwd_work(y.numel() // cout, cout), device=y.device,
+                           dtype=torch.float32)
+        dy, dres = bn_bwd(L, layer, ctx, mode, dout,
+                          in_mask if in_mask is not None else ctx.get("mask"),
+                          ctx.pop("pre_sums", None) or {}, work,
+                          want_dres=ctx["has_res"] and not masked_res)
         if phase == 1:
             ctx["_bn_out"] = (dy, dres)
             return None
-    # weight gradient: on the Program's side stream when it has one (off the critical
-    # path; overlaps the following dgrad / BN-backward chain).  Tensors it reads that the
-    # main stream allocated are recorded on the side stream so the caching allocator does
-    # not hand their memory out again before the wgrad has read them.
-    pre = ctx.get("pre")
-    side = getattr(layer._prog, "_wgrad_stream", None)
-
-    def launch_wgrad():
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-            for t in (x, dy) + (tuple(pre) if pre is not None else ()):
-                t.record_stream(side)
-        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-            slab = torch.empty(S * cout * K, device=y.device, dtype=torch.float32)
-            pre_kw = {}
-            xw = x
-            if pre is not None:
-                if _can(wcfg, "pre_bn", L, wgrad=True):
-                    pre_kw = dict(pre_scale=pre[0], pre_shift=pre[1])
-                else:
-                    xw = _materialise(x, pre)
-            L.conv_wgrad(xw, dy, layer.grad_slot("weight"), slab, layer.cin, k, k, s, p, acc, S,
-                         wcfg, s2d, **pre_kw)
-
-    launch_wgrad()
-    dx = None
-    if need_dx and not ctx["first"]:
-        _, wd = packed_weights(layer, need_wd=True)
-        N_, H, W, Cin = x.shape
-        cfg = dgrad_cfg(N_ * H * W, Cin, k, s, cout, W)
-        if dx_into is not None:
-            dx = dx_into
-            L.conv_dgrad(dy, wd, dx_into, k, k, s, p, dx_into, cfg)
-        else:
-            dx = empty_nhwc(N_, H, W, Cin, x)
-            merge_kw = {}
-            if (shortcut is not None and s == 2 and k == 3 and p == 1 and dx_add is None
-                    and _can(cfg, "multi_merge_red", L)
-                    and H % 2 == 0 and W % 2 == 0):
-                dy2, wd2 = shortcut["join"]()
-                if (dy2.shape[:3] == dy.shape[:3] and dy2.shape[3] % 64 == 0
-                        and (not _can(cfg, "merge_same_c", L) or dy2.shape[3] == dy.shape[3])):
-                    merge_kw = dict(dy2=dy2, wd2=wd2)
-                    shortcut["merged"] = True
-            red_kw = (_dgrad_red(L, red_for, cfg, s, dx, complete_s2=bool(merge_kw))
-                      if red_for is not None else {})
-            if isinstance(dx_add, tuple):
-                L.conv_dgrad(dy, wd, dx, k, k, s, p, dx_add[1], cfg, add_mask=dx_add[2], **red_kw)
-            else:
-                L.conv_dgrad(dy, wd, dx, k, k, s, p, dx_add, cfg, **red_kw, **merge_kw)
+    # 3. weight gradient.  red_for is the stem (a pooled ConvBN) only for the first block's c1:
+    # the step's last conv
+    tail = red_for is not None and bool(getattr(red_for[0], "pool_k", 0))
+    launch_wgrad(L, layer, ctx["x"], dy, ctx.get("pre"), k, s, p, tail=tail)
+    # 4. data gradient
+    dx = (_dgrad(L, layer, ctx["x"], dy, k, s, p, dx_add, dx_into, red_for, shortcut)
+          if need_dx else None)
     if ctx["has_res"]:
         return dx, (("masked", dout, ctx["mask"]) if masked_res else dres)
+    return dx
+
+
+def bn_bwd(L, layer, ctx, mode, dout, mask, pre_sums, work, want_dres=False):
+    """Shared backward step (interior layers and dmlab.ops.stem): BN backward of ``dout`` in
+    ``mode`` (0 linear, 1 / 2 / 4 ReLU mask from ctx["out"] / y / ``mask``, 3: ``dout`` is the
+    max-pool's output gradient, gathered through ctx["idx"]); ``pre_sums``: Î£dz, Î£dzÂ·xÌ‚ already
+    reduced.  Writes dgamma / dbeta and returns (dy, dres); dres only when ``want_dres``."""
+    y = ctx["y"]
+    cout = y.shape[3]
+    dy = empty_nhwc(*y.shape, y)
+    dres = empty_nhwc(*y.shape, y) if want_dres else None
+    acc = 1.0 if layer.accumulate else 0.0
+    pooled = mode == 3
+    bn_args = (None if pooled else dout, ctx.get("out"), y, ctx["mean"], ctx["invstd"],
+               layer.bn_weight.detach(), layer.grad_slot("bn_weight"),
+               layer.grad_slot("bn_bias"), acc, mode, ctx["scale"], ctx["shift"],
+               dout if pooled else None, ctx.get("idx"),
+               getattr(layer, "pool_k", 3), getattr(layer, "pool_s", 2),
+               getattr(layer, "pool_p", 1), dy, dres, work)
+    total = ctx.get("total")
+    if total is None:
+        L.bn_backward(*bn_args, mask=mask, **pre_sums)
+    else:
+        # synchronized BatchNorm.  stage "sums": this rank's Î£dz, Î£dzÂ·xÌ‚ (reduced here or taken
+        # from pre_sums) -> dgamma / dbeta and a float64 row; all-reduce; stage "apply": the
+        # coefficients from the global sums and count, then the same apply kernels
+        sums = torch.empty(2 * cout, device=y.device, dtype=torch.float64)
+        L.bn_backward(*bn_args, mask=mask, stage=1, sums=sums, **pre_sums)
+        layer._sync_bn.reduce_sums(sums)
+        L.bn_backward(*bn_args, mask=mask, stage=2, sums=sums, total=total)
+    return dy, dres
+
+
+def launch_wgrad(L, layer, x, dy, pre, k, s, p, s2d=False, tail=False):
+    """Shared backward step (interior layers and dmlab.ops.stem): dW from x (``pre``: consumed
+    as relu(x*scale + shift); ``s2d``: x is the stem's space-to-depth packing) and dy into the
+    layer's OIHW fp32 grad slot.  On the Program's side stream when it has one (off the critical
+    path; overlaps the following dgrad / BN-backward chain).  Tensors it reads that the main
+    stream allocated are recorded on the side stream so the caching allocator does not hand
+    their memory out again before the wgrad has read them."""
+    N, OH, OW, cout = dy.shape
+    C = x.shape[3]
+    K = k * k * C
+    same = not s2d and (OH, OW) == tuple(x.shape[1:3])
+    even = OW if (not s2d and 2 * OH == x.shape[1] and 2 * OW == x.shape[2]) else 0
+    wcfg, S = _wgrad_plan(N * OH * OW, cout, K, k, s, C, W=OW if same else 0,
+                          rows=N * OH if same else 0, tail=tail, even=even)
+    side = getattr(layer._prog, "_wgrad_stream", None)
+    if side is not None:
+        side.wait_stream(torch.cuda.current_stream())
+        for t in (x, dy) + (tuple(pre) if pre is not None else ()):
+            t.record_stream(side)
+    with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+        slab = torch.empty(S * cout * K, device=dy.device, dtype=torch.float32)
+        pre_kw = {}
+        if pre is not None:
+            if _can(wcfg, "pre_bn", L, wgrad=True):
+                pre_kw = dict(pre_scale=pre[0], pre_shift=pre[1])
+            else:
+                x = _materialise(x, pre)
+        L.conv_wgrad(x, dy, layer.grad_slot("weight"), slab, layer.cin, k, k, s, p,
+                     1.0 if layer.accumulate else 0.0, S, wcfg, s2d, **pre_kw)
+
+
+def _dgrad(L, layer, x, dy, k, s, p, dx_add, dx_into, red_for, shortcut):
+    """Data gradient of an interior ConvBN (convbn_bwd documents the options); returns dx."""
+    cout = dy.shape[3]
+    _, wd = packed_weights(layer, need_wd=True)
+    N, H, W, Cin = x.shape
+    cfg = dgrad_cfg(N * H * W, Cin, k, s, cout, W)
+    if dx_into is not None:
+        L.conv_dgrad(dy, wd, dx_into, k, k, s, p, dx_into, cfg)
+        return dx_into
+    dx = empty_nhwc(N, H, W, Cin, x)
+    merge_kw = {}
+    if (shortcut is not None and s == 2 and k == 3 and p == 1 and dx_add is None
+            and _can(cfg, "multi_merge_red", L)
+            and H % 2 == 0 and W % 2 == 0):
+        dy2, wd2 = shortcut["join"]()
+        if (dy2.shape[:3] == dy.shape[:3] and dy2.shape[3] % 64 == 0
+                and (not _can(cfg, "merge_same_c", L) or dy2.shape[3] == dy.shape[3])):
+            merge_kw = dict(dy2=dy2, wd2=wd2)
+            shortcut["merged"] = True
+    red_kw = (_dgrad_red(L, red_for, cfg, s, dx, complete_s2=bool(merge_kw))
+              if red_for is not None else {})
+    if isinstance(dx_add, tuple):
+        L.conv_dgrad(dy, wd, dx, k, k, s, p, dx_add[1], cfg, add_mask=dx_add[2], **red_kw)
+    else:
+        L.conv_dgrad(dy, wd, dx, k, k, s, p, dx_add, cfg, **red_kw, **merge_kw)
     return dx

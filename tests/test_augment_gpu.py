@@ -220,7 +220,7 @@ def test_resnet18_step_through_the_loader(dev):
 
     from dmlab.models import ResNet18
     from dmlab.nn import cross_entropy
-    from dmlab.ops.convbn import stem_fused_ok
+    from dmlab.ops.stem import stem_fused_ok
 
     n, side = 32, 64
     g = torch.Generator().manual_seed(12)
